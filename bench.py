@@ -19,6 +19,10 @@ pa_device_malloc, every byte of the data plane moves through pa_comm (RCCL over 
 (checked 1 MB all-to-all + all-reduce + all-gather under a watchdog) before the first step.  (Checker workloads of the CPU tests
 bring torch.distributed themselves: for them the control plane is the gloo group.)
 
+Plain run and --full.  `bench.py --gpus N --steps K --warmup W` sets up, warms up, times the K headline steps, writes their outputs
+when --dump-outputs is given, and prints the line: the contract's keys and `roofline` (from the HIP events of the timed steps
+themselves).  The side legs (`cpu_baseline`, `q3`, `h2d`, `sf300`, `operators`, the other scaling mode) run only with --full.
+
 Output.  ONE JSON line of at most 4 KB on rank 0's stdout: the contract's keys, `roofline`, `cpu_baseline` and one-number
 summaries of the side legs.  Everything else -- per-stage times, results, operator benchmark entries, samples' descriptions --
 goes to the detail file (`--detail`, default bench_detail.json next to this file) and to stderr.
@@ -86,7 +90,15 @@ def parse_args(argv=None):
                     "on the host), N = 1 only; 0 = skip")
     ap.add_argument("--workload", default="device", help="'device' = the product path; 'module:Class' = a checker workload with the same "
                     "surface (tests/rehearsal_workload.py: the oracle's operators on CPU ranks, to rehearse the multi-rank control flow)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also run the side legs: Q3, the other scaling mode, host pages, SF300, the operator "
+                    "benchmarks and the CPU baselines (--q3, --other-scaling, --h2d-rows, --sf300, --operators, --cpu-rows select among them).  "
+                    "Without it a run sets up, warms up, times the headline steps and prints the line, nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the headline's last step computed "
+                    "as DIR/<query>.npy (float64), so that two builds can be compared output for output")
+    args = ap.parse_args(argv)
+    if not args.full:   # the side legs take minutes of their own: a plain run measures the headline only
+        args.q3 = args.other_scaling = args.h2d_rows = args.sf300 = args.operators = args.cpu_rows = 0
+    return args
 
 
 def launch_ranks(args, argv):
@@ -613,6 +625,22 @@ def printable(rows):
     return [[x.decode() if isinstance(x, bytes) else x for x in r] for r in rows]
 
 
+def dump_outputs(workload, out_dir):
+    """--dump-outputs: the rows the headline's operators handed back in the last step, one float64 array per query
+    (DIR/<query>.npy, one row per output row; a VARCHAR key as the big-endian integer of its bytes, a null as NaN).  Rows are
+    sorted: a hash aggregation emits its groups in no defined order."""
+    import numpy as np
+
+    def number(x):
+        if isinstance(x, bytes):
+            return float(int.from_bytes(x, "big"))
+        return float("nan") if x is None else float(x)
+    os.makedirs(out_dir, exist_ok=True)
+    for name in workload.queries:
+        rows = sorted(tuple(number(x) for x in r) for r in workload.results[name])
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(rows, dtype=np.float64))
+
+
 def sf300_leg(args, dist, device, steps=3):
     """BASELINE config #5's tables on one GPU: Q1+Q6 over 1.80 G lineitem rows (82.8 GB of columns) and Q3 over the SF300
     customer / orders / lineitem tables, `steps` timed steps each after one warm-up step.  The SF100 tables of the headline
@@ -839,6 +867,8 @@ def main(argv=None, workload_factory=None, out=None):
 
     elapsed = timed_region(workload, dist, world, workload.step, args.steps, args.warmup)
     value = job_rows(workload) * args.steps / elapsed
+    if args.dump_outputs and rank == 0:   # (with more than one rank the FINAL results are rank 0's)
+        dump_outputs(workload, args.dump_outputs)
 
     # HBM bytes per launch from the committed rocprofv3 PMC passes (profiles/pmc_traffic.json, written by
     # scripts/summarize_profile.py), keyed by kernel name: a kernel whose generated code changed has another name and gets null

@@ -273,7 +273,7 @@ def bench_worker(rank, world, port, result_queue):
 
     out = io.StringIO()
     detail = os.path.join(os.environ.get("BENCH_TEST_DIR", "/tmp"), "bench_detail_8.json")
-    bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--sf", "0.002", "--cpu-rows", "0", "--backend", "gloo", "--scaling", "weak",
+    bench.main(["--full", "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sf", "0.002", "--cpu-rows", "0", "--backend", "gloo", "--scaling", "weak",
                 "--detail", detail], workload_factory=factory, out=out)
     result_queue.put((rank, out.getvalue(), seen["w"].results.get("q3")))
 
@@ -343,7 +343,7 @@ def bench_worker_one_rank_fails(rank, world, port, path):
             return super().q3_step()
 
     with open("%s.%d" % (path, rank), "w") as out:
-        sys.exit(bench.main(["--gpus", str(world), "--steps", "1", "--warmup", "1", "--sf", "0.002", "--cpu-rows", "0", "--backend", "gloo",
+        sys.exit(bench.main(["--full", "--gpus", str(world), "--steps", "1", "--warmup", "1", "--sf", "0.002", "--cpu-rows", "0", "--backend", "gloo",
                              "--q3-timeout", "8", "--other-scaling", "0", "--detail", path + ".detail"], workload_factory=FailsOnRankOne, out=out))
 
 
@@ -392,6 +392,39 @@ def check_q1_q6(results, q6_sum, q1_rows):
         assert all(abs(a - b) <= 1e-9 * abs(b) for a, b in zip(g[2:-1], e[2:-1]))
 
 
+SIDE_LEGS = ("q3", "strong", "weak", "cpu_baseline", "h2d", "sf300", "operators")
+
+
+def check_dumped_q1_q6(out_dir, q6_sum, q1_rows):
+    """--dump-outputs: q6.npy / q1.npy, float64, one row per output row in key order (VARCHAR(1) keys as their byte)."""
+    import numpy as np
+    assert sorted(os.listdir(out_dir)) == ["q1.npy", "q6.npy"]
+    q6, q1 = np.load(os.path.join(out_dir, "q6.npy")), np.load(os.path.join(out_dir, "q1.npy"))
+    assert q6.dtype == q1.dtype == np.float64 and q6.shape == (1, 1) and q1.shape == (len(q1_rows), 10)
+    assert abs(q6[0, 0] - q6_sum) <= 1e-9 * abs(q6_sum)
+    for g, e in zip(q1, q1_rows):
+        assert list(g[:2]) == [e[0][0], e[1][0]] and g[-1] == e[-1]
+        assert all(abs(a - b) <= 1e-9 * abs(b) for a, b in zip(g[2:-1], e[2:-1]))
+
+
+def test_plain_bench_times_the_headline_only_and_dumps_its_outputs(oracle, tmp_path):
+    """Without --full the run holds the headline and nothing of the side legs (no Q3 leg, no other scaling mode), `steps` is what was
+    asked for, and --dump-outputs writes rank 0's merged results of the last step: those of one process over the whole table."""
+    from presto_amd import tpch
+    sf = 0.002
+    path, out = str(tmp_path / "detail.json"), str(tmp_path / "outputs")
+    r = run_bench(["--gpus", "2", "--backend", "gloo", "--workload", "tests.rehearsal_workload:RehearsalWorkload", "--sf", str(sf), "--steps", "3",
+                   "--warmup", "1", "--detail", path, "--dump-outputs", out])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    line = check_line_shape(r.stdout.decode())
+    detail = json.load(open(path))
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["n_gpus"] == 2
+    assert not [k for k in SIDE_LEGS if k in line or k in detail]
+    rows = tpch.lineitem_rows(sf)
+    check_q1_q6(detail["results"], *oracle_q1_q6(oracle, sf, rows))
+    check_dumped_q1_q6(out, *oracle_q1_q6(oracle, sf, rows))
+
+
 def test_bench_launches_its_own_ranks(oracle, tmp_path):
     """`python bench.py --gpus 8` with no torchrun environment starts 8 ranks itself (before anything touches a GPU), prints ONE
     line with n_gpus 8, the STRONG headline (the metric's mode: the ONE SF table split by row range) and the `weak` object, both with
@@ -399,7 +432,7 @@ def test_bench_launches_its_own_ranks(oracle, tmp_path):
     from presto_amd import tpch
     world, sf = 8, 0.002
     path = str(tmp_path / "detail.json")
-    r = run_bench(["--gpus", str(world), "--backend", "gloo", "--workload", "tests.rehearsal_workload:RehearsalWorkload", "--sf", str(sf),
+    r = run_bench(["--full", "--gpus", str(world), "--backend", "gloo", "--workload", "tests.rehearsal_workload:RehearsalWorkload", "--sf", str(sf),
                    "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--detail", path])
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = check_line_shape(r.stdout.decode())
@@ -418,7 +451,7 @@ def test_bench_weak_headline_on_two_ranks(oracle, tmp_path):
     from presto_amd import tpch
     sf = 0.002
     path = str(tmp_path / "detail.json")
-    r = run_bench(["--gpus", "2", "--backend", "gloo", "--workload", "tests.rehearsal_workload:RehearsalWorkload", "--sf", str(sf), "--steps", "1",
+    r = run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--workload", "tests.rehearsal_workload:RehearsalWorkload", "--sf", str(sf), "--steps", "1",
                    "--warmup", "1", "--cpu-rows", "0", "--scaling", "weak", "--q3", "0", "--detail", path])
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     line = check_line_shape(r.stdout.decode())

@@ -6,7 +6,7 @@ import json
 import pytest
 
 from presto_amd import tpch
-from tests.test_exchange_gloo import check_line_shape, check_q1_q6, oracle_q1_q6, run_bench
+from tests.test_exchange_gloo import SIDE_LEGS, check_dumped_q1_q6, check_line_shape, check_q1_q6, oracle_q1_q6, run_bench
 
 pytestmark = pytest.mark.gpu
 
@@ -16,7 +16,7 @@ def test_bench_two_ranks_as_a_plain_subprocess(gpu, oracle, tmp_path):
     that finds it imported leaves with exit code 5): control plane = presto_amd/control.py, one ROCm stack per process."""
     sf = 0.05
     path = str(tmp_path / "detail.json")
-    r = run_bench(["--gpus", "2", "--backend", "gloo", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--detail", path], timeout=900)
+    r = run_bench(["--full", "--gpus", "2", "--backend", "gloo", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--detail", path], timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = check_line_shape(r.stdout.decode())
     d = json.load(open(path))
@@ -39,7 +39,7 @@ def test_bench_goes_on_over_the_host_transport_when_rccl_refuses(gpu, oracle, tm
     results equal to the oracle's -- without the Q3 leg; the line says what happened (config.data_plane, q3.error) and the exit code is 0."""
     sf = 0.05
     path = str(tmp_path / "detail.json")
-    r = run_bench(["--gpus", "2", "--backend", "nccl", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--preflight-timeout", "60",
+    r = run_bench(["--full", "--gpus", "2", "--backend", "nccl", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "0", "--preflight-timeout", "60",
                    "--detail", path], timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = check_line_shape(r.stdout.decode())
@@ -54,10 +54,10 @@ def test_bench_goes_on_over_the_host_transport_when_rccl_refuses(gpu, oracle, tm
 
 
 def test_bench_one_rank_default_shape_small(gpu, oracle, tmp_path):
-    """`--gpus 1`: no launcher, no merge; the side legs are all in the detail file, their one-number summaries in the line."""
+    """`--gpus 1 --full`: no launcher, no merge; the side legs are all in the detail file, their one-number summaries in the line."""
     sf = 0.05
     path = str(tmp_path / "detail.json")
-    r = run_bench(["--gpus", "1", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "200000", "--h2d-rows", "100000", "--detail", path],
+    r = run_bench(["--full", "--gpus", "1", "--sf", str(sf), "--steps", "2", "--warmup", "1", "--cpu-rows", "200000", "--h2d-rows", "100000", "--detail", path],
                   timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     summary = check_line_shape(r.stdout.decode())
@@ -87,3 +87,21 @@ def test_bench_one_rank_default_shape_small(gpu, oracle, tmp_path):
     assert 120_000 < by_case["8 M build rows x1, 1.4 M probe rows, match rate 0.1"]["probe"]["matches"] < 160_000
     assert 6_900_000 < by_case["8 M build rows x5, 1.4 M probe rows, match rate 1"]["probe"]["matches"] < 7_100_000
     assert ops["order_by"]["value"] > 0 and ops["topn"]["value"] > 0 and ops["topn"]["cpu"]["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only(gpu, oracle, tmp_path):
+    """`--gpus 1` without --full: the headline and the rooflines of its two kernels (from the timed steps' own HIP events), no side leg;
+    --dump-outputs writes the Q1 / Q6 rows of the last timed step, equal to the oracle's."""
+    sf = 0.05
+    path, out = str(tmp_path / "detail.json"), str(tmp_path / "outputs")
+    r = run_bench(["--gpus", "1", "--sf", str(sf), "--steps", "3", "--warmup", "1", "--detail", path, "--dump-outputs", out], timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    line = check_line_shape(r.stdout.decode())
+    d = json.load(open(path))
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["ms_per_step"] > 0 and d["torch_imported"] is False
+    assert line["roofline"]["kernel"].startswith("pa_fused_lds_") and line["roofline"]["launches"] > 0
+    assert line["roofline_q6"]["kernel"].startswith("pa_fused_global_")
+    assert not [k for k in SIDE_LEGS if k in line or k in d]
+    rows = tpch.lineitem_rows(sf)
+    check_q1_q6(d["results"], *oracle_q1_q6(oracle, sf, rows))
+    check_dumped_q1_q6(out, *oracle_q1_q6(oracle, sf, rows))
