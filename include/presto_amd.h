@@ -772,6 +772,9 @@ int32_t pa_tpch_generate(int32_t column, double scale_factor, int64_t first_row,
  * variant: -1 default, 0 GLOBAL (no keys), 1 LDS (few groups), 2 GT (HBM table). */
 int64_t pa_codegen_fused(const pa_fused_aggregation_desc* desc, int32_t variant, char* buf, int64_t buf_size, char* key);
 int64_t pa_codegen_compile_fused(const pa_fused_aggregation_desc* desc, int32_t variant);
+/* the staged-load plan of a descriptor: per input channel (channel_stage[0 .. n)) the stage that loads it, -1 = not read; returns the
+ * number of stages (< 2: the plan does not stage its loads).  variant 9 of pa_codegen_fused* is the staged GLOBAL kernel. */
+int32_t pa_codegen_fused_stages(const pa_fused_aggregation_desc* desc, int32_t* channel_stage, int32_t n);
 /* the same for ANY column-layout signature and every tier: nullable_channels = bit c set when input channel c carries a valueIsNull
  * array (kernels are generated per signature); variant 0 GLOBAL, 1 LDS (register key table), 2 GT (HBM table), 3 LDSH (LDS table per
  * workgroup), 4 the hash-partition pass, 5 LDSP (partition-owned LDS tables).  buf may be NULL; compile != 0 also compiles the unit with

@@ -91,6 +91,8 @@ def lib():
     L.pa_tpch_generate.argtypes = [C.c_int32, C.c_double, C.c_int64, C.c_int64, C.c_uint64, vp, vp, vp]
     L.pa_codegen_fused.argtypes = [C.POINTER(abi.pa_fused_aggregation_desc), C.c_int32, C.c_char_p, C.c_int64, C.c_char_p]
     L.pa_codegen_fused.restype = C.c_int64
+    L.pa_codegen_fused_stages.argtypes = [C.POINTER(abi.pa_fused_aggregation_desc), C.POINTER(C.c_int32), C.c_int32]
+    L.pa_codegen_fused_stages.restype = C.c_int32
     L.pa_codegen_compile_fused.argtypes = [C.POINTER(abi.pa_fused_aggregation_desc), C.c_int32]
     L.pa_codegen_compile_fused.restype = C.c_int64
     L.pa_codegen_filter_project.argtypes = [C.POINTER(abi.pa_filter_project_desc), C.c_char_p, C.c_int64, C.c_char_p]

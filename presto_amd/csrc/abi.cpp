@@ -1091,6 +1091,16 @@ int64_t pa_codegen_fused(const pa_fused_aggregation_desc* desc, int32_t variant,
     return rc < 0 ? rc : need;
 }
 
+int32_t pa_codegen_fused_stages(const pa_fused_aggregation_desc* desc, int32_t* channel_stage, int32_t n)
+{
+    int32_t stages = 0;
+    int32_t rc = guarded([&]() -> int32_t {
+        stages = fused_stages_for_desc(desc, channel_stage, n);
+        return PA_OK;
+    });
+    return rc < 0 ? rc : stages;
+}
+
 int64_t pa_codegen_fused_layout(const pa_fused_aggregation_desc* desc, int32_t variant, uint64_t nullable_channels, int32_t compile, char* buf,
                                 int64_t buf_size)
 {

@@ -57,11 +57,12 @@ public:
     // Appends statements computing `e` to `out` and returns the result names.
     GenValue emit(const OwnedExpr& e, std::ostringstream& out);
     static std::string ctype(int32_t type);
+    // may evaluating node `id` raise an error (integer / long decimal arithmetic, decimal casts)?
+    bool can_throw(const OwnedExpr& e, int32_t id) const;
 
 private:
     GenValue emit_node(const OwnedExpr& e, int32_t id, std::ostringstream& out);
     GenValue emit_compare(int32_t op, const GenValue& a, const GenValue& b, std::ostringstream& out);
-    bool can_throw(const OwnedExpr& e, int32_t id) const;
     std::string fresh(const char* prefix);
     static std::string or_nulls(const std::vector<std::string>& ns);
 

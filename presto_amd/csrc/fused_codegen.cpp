@@ -55,13 +55,18 @@ KernelInfo FusedGen::run()
         PA_REQUIRE(!s.join, PA_ERR_NOT_SUPPORTED, "no range-table variant behind a probe stage");
         variant = variant == V_GLOBAL_R ? V_GLOBAL : V_LDS;
     }
+    if (variant == V_GLOBAL_S) {
+        PA_REQUIRE(!s.join && s.n_stages >= 2 && s.group_proj.empty(), PA_ERR_NOT_SUPPORTED, "no staged variant for this plan");
+        staged = true;
+        variant = V_GLOBAL;
+    }
     k.variant = variant;
     k.ranged = ranged;
     // entry names carry the tier (and "probe" behind a probe stage); the translation unit appends the first 8 hex digits of the
     // code object's key (PA_K, jit.cpp), so that a kernel trace tells the plans apart: pa_fused_lds_<key8>, pa_fused_probe_brow_<key8> ...
     {
         static const char* const kTierName[] = {"global", "lds", "gt", "ldsh", "hash", "ldsp", "brow"};
-        k.entry = std::string("pa_fused_") + (s.join ? "probe_" : "") + kTierName[variant] + (ranged ? "_ranges" : "");
+        k.entry = std::string("pa_fused_") + (s.join ? "probe_" : "") + kTierName[variant] + (ranged ? "_ranges" : "") + (staged ? "_staged" : "");
     }
     k.block = variant == V_LDS ? 64 : 256;
     k.c = variant == V_LDS ? kLdsSlots : 0;
@@ -72,6 +77,10 @@ KernelInfo FusedGen::run()
     ri.used = s.used_channel;
     for (int c = 0; c < s.n_in; c++) ri.used[c] = s.used_channel[c] && !s.lazy_channel[c];
     ri.short_bound = s.short_bound;
+    if (staged) {
+        std::vector<VectorVar> vars;
+        PA_REQUIRE(vector_load_vars(ri, layout, vars), PA_ERR_NOT_SUPPORTED, "no staged variant for these column types");
+    }
     brow = variant == V_BROW;
     lds_table = variant == V_LDSH || variant == V_LDSP;
     gt_like = variant == V_GT;  // a thread-private pending run in front of the table
@@ -102,6 +111,7 @@ KernelInfo FusedGen::run()
     if (s.join) probe_build_loads();
     row_function();
     if (s.join) probe_row_composition();
+    if (staged) staged_row_functions();
 
     // kernels.  mode 0: one kernel walks the page (GLOBAL / GT).  LDS variant: the wave's key table is wave-uniform
     // state, so every lane must take part in every pa_row call; the host splits the page and `pa_fused` (mode 1) takes the
@@ -395,13 +405,13 @@ void FusedGen::state_layout_id()
 
 // The row function: pa_row(a, acc, live, row, <column values>) -- behind a probe stage pa_pre / pa_post, and pa_row their
 // composition (fused_tier_probe.cpp).
-void FusedGen::row_function()
+void FusedGen::row_function(const std::string& name)
 {
     if (s.join) {
         probe_row_frames();
     }
     else {
-        src << "__device__ __forceinline__ void pa_row(const PaFusedArgs& a, PaAcc& acc, const bool live, const i32 row" << row_params(ri, layout) << ")\n{\n";
+        src << "__device__ __forceinline__ void " << name << "(const PaFusedArgs& a, PaAcc& acc, const bool live, const i32 row" << row_params(ri, layout) << ")\n{\n";
     }
     src << body.str();
     // values needed after the selected-only block are declared up front
@@ -530,6 +540,11 @@ void FusedGen::page_loop()
     src << "    const i64 nq = a.vec ? (a.n >> 2) : 0;\n";
     const std::string tail_rows = "    for (i64 r = (nq << 2) + t; r < a.n; r += T) {\n        pa_row(a, acc, true, (i32)r" + scalar_args(ri, layout) + ");" + flush + "\n    }\n";
     bool two_loops = false;
+    if (staged) {
+        staged_page_loop();
+        src << tail_rows;
+        return;
+    }
     if (brow) {
         int level = 3;
         if (const char* e = getenv("PRESTO_AMD_BROW_PIPE")) level = atoi(e);  // (measurement switch: 0 = one quad at a time)

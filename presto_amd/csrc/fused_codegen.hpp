@@ -75,6 +75,7 @@ struct FusedGen {
     std::vector<WordDef> words;
     std::map<std::string, int> word_index;
     bool brow = false, lds_table = false, gt_like = false;
+    bool staged = false;               // V_GLOBAL_S: the page loop of the staged plan (fused_tier_global.cpp)
     std::string lazy_params, lazy_names;
     int B = 256;                       // workgroup size
     std::string flush;                 // what ends a thread's pending run behind a quad / a row (GT, BROW), or nothing
@@ -90,7 +91,7 @@ struct FusedGen {
     void group_keys();
     void accumulator_words();
     void state_layout_id();
-    void row_function();
+    void row_function(const std::string& name = "pa_row");
     void emit_quad(const std::string (&args)[4]);
     void emit_kernel(const std::string& name, int mode);
     void ranges_loop();
@@ -103,6 +104,8 @@ struct FusedGen {
     void global_kernel_begin();
     void global_thread_ids();
     void global_kernel_end();
+    void staged_row_functions();
+    void staged_page_loop();
 
     // ---- LDS (fused_tier_lds.cpp) ----
     void lds_check_capacity();

@@ -292,6 +292,72 @@ void finalize_spec(Spec& s)
     for (int c = 0; c < s.n_in; c++) {
         if (s.derived(c) || s.in_types[c] == PA_VARCHAR) s.lazy_channel[c] = false;  // strings are handed to the row function whole
     }
+    plan_stages(s);
+}
+
+// The staged plan (Spec::conjuncts .. n_stages).  Conjunct k is evaluated only where conjuncts 0 .. k-1 were not FALSE -- a FALSE
+// conjunct decides the AND, and the short-circuit AND (AndCodeGenerator) hides the errors of the conjuncts to its right -- so a
+// channel is loaded from the stage of the first conjunct that reads it on.
+void plan_stages(Spec& s)
+{
+    s.conjuncts.clear();
+    s.conjunct_begin.clear();
+    s.channel_stage.assign(s.n_in, -1);
+    s.n_stages = 0;
+    for (int c = 0; c < s.n_in; c++) {
+        if (s.used_channel[c]) s.channel_stage[c] = 0;
+    }
+    if (s.join || !s.has_filter) return;
+    std::vector<int32_t> todo{s.filter.root};
+    while (!todo.empty()) {  // depth first, left to right: nested ANDs flatten in the written order
+        const int32_t id = todo.back();
+        todo.pop_back();
+        const pa_expr_node& n = s.filter.node(id);
+        if (n.kind == PA_EXPR_SPECIAL && n.op == PA_FORM_AND) {
+            const int32_t* a = s.filter.node_args(id);
+            for (int32_t k = n.nargs - 1; k >= 0; k--) todo.push_back(a[k]);
+        }
+        else {
+            s.conjuncts.push_back(id);
+        }
+    }
+    // per channel: the first conjunct that reads it; stages begin at the conjuncts that read a channel first
+    std::vector<int> first(s.n_in, -1);
+    std::vector<int> begins;
+    for (size_t j = 0; j < s.conjuncts.size(); j++) {
+        std::set<int32_t> ch;
+        OwnedExpr sub = s.filter;
+        sub.root = s.conjuncts[j];
+        sub.collect_channels(&ch);
+        bool starts = j == 0;
+        for (int32_t c : ch) {
+            if (c < 0 || c >= s.n_in || first[c] >= 0) continue;
+            first[c] = (int)j;
+            starts = true;
+        }
+        if (starts) begins.push_back((int)j);
+    }
+    // what only the projections, keys and aggregates read: one last stage, loaded for the selected rows
+    bool tail = false;
+    for (int c = 0; c < s.n_in; c++) tail = tail || (s.used_channel[c] && first[c] < 0);
+    if (tail) begins.push_back((int)s.conjuncts.size());
+    if ((int)begins.size() > kMaxStages) begins.resize(kMaxStages);  // stages beyond the fourth merge into it
+    for (int c = 0; c < s.n_in; c++) {
+        if (!s.used_channel[c]) continue;
+        int st = 0;
+        if (s.derived(c) || s.in_types[c] == PA_VARCHAR) {
+            st = 0;  // strings and derived channels stay eager
+        }
+        else {
+            const int at = first[c] < 0 ? (int)s.conjuncts.size() : first[c];
+            for (size_t k = 0; k < begins.size(); k++) {
+                if (begins[k] <= at) st = (int)k;
+            }
+        }
+        s.channel_stage[c] = st;
+    }
+    s.conjunct_begin = begins;
+    s.n_stages = (int)begins.size();
 }
 
 }  // namespace fused

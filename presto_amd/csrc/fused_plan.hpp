@@ -70,7 +70,9 @@ struct FusedArgs {
 // V_BROW: probe stage whose group keys are functions of the build row: the table slot is the build position
 // V_GLOBAL_R / V_LDS_R: the ungrouped / few-groups kernels over a TABLE of row ranges (stable device pages that do not continue
 // each other in memory, taken in place by one launch: see ranges_)
-enum Variant { V_GLOBAL = 0, V_LDS = 1, V_GT = 2, V_LDSH = 3, V_HASH = 4, V_LDSP = 5, V_BROW = 6, V_GLOBAL_R = 7, V_LDS_R = 8 };
+// V_GLOBAL_S: the ungrouped kernel whose page loop loads the columns of a staged plan (Spec::n_stages) only for the rows still alive
+enum Variant { V_GLOBAL = 0, V_LDS = 1, V_GT = 2, V_LDSH = 3, V_HASH = 4, V_LDSP = 5, V_BROW = 6, V_GLOBAL_R = 7, V_LDS_R = 8, V_GLOBAL_S = 9 };
+constexpr int kMaxStages = 4;
 // rows per entry of a range table: one workgroup takes an entry at a time
 constexpr int64_t kRangeRows = 8192, kRangeRowsLds = 4096;
 enum WordKind { W_CNT = 0, W_SUMF = 1, W_SUMI = 2, W_MAXU = 3 };
@@ -105,6 +107,14 @@ struct Spec {
     // per channel: read inside the selected-rows block only (probe stage: everything the filter and the probe key do not need
     // is loaded for the rows that found a match, not for the whole page)
     std::vector<bool> lazy_channel;
+    // Staged loads (no probe stage, a filter): the filter's top-level AND flattened into its conjuncts, in the written order
+    // (node ids of `filter`), and per used channel the stage that loads it -- stage k evaluates conjuncts conjunct_begin[k] ..
+    // conjunct_begin[k + 1] - 1 for the rows still alive and then asks for the channels of stage k + 1; the last stage loads what
+    // only the projections read and accumulates.  n_stages < 2: no staging (channel_stage all 0 or -1 for unused channels).
+    std::vector<int32_t> conjuncts;
+    std::vector<int> conjunct_begin;  // per stage (n_stages entries; the last stage evaluates no conjunct when it is the projections')
+    std::vector<int> channel_stage;   // per channel: -1 unused
+    int n_stages = 0;
     int n_in = 0;
     std::vector<int32_t> in_types, in_params;
     bool has_filter = false;
@@ -139,6 +149,9 @@ struct KernelInfo {
     std::string source, entry;
     int variant = V_GLOBAL;
     bool ranged = false;  // the kernel walks a table of row ranges (V_GLOBAL_R / V_LDS_R; `variant` names the base variant)
+    // V_GLOBAL_S: bytes per row each stage loads (values and NULL flags); the kernel writes, per workgroup, the rows that asked for
+    // the columns of stage 1 .. n - 1 into slab words gridDim.x * nw + blockIdx.x * (n - 1) + k - 1 (the decision: op_fused.hpp)
+    std::vector<int> stage_bytes;
     int nw = 0, w = 0, c = 0, block = 256;
     int lc = 0;  // V_LDSH: slots of the workgroup's LDS table
     // V_BROW: the accumulator word every row of a group updates -- "this build row has a group" is read off it (its value differs
@@ -167,6 +180,8 @@ Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc&
 Spec make_spec(const pa_fused_aggregation_desc* d);
 // channels read, short / interned VARCHAR keys: everything of a Spec that follows from its expressions and aggregates
 void finalize_spec(Spec& s);
+// the staged plan of a Spec (Spec::conjuncts .. n_stages; part of finalize_spec)
+void plan_stages(Spec& s);
 
 // Words of a range-table entry, in this order: per used channel its values pointer, its offsets pointer when it is a VARCHAR
 // channel, its NULL flags pointer when the layout calls it nullable; then rows | (vec << 32).

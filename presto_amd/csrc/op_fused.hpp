@@ -910,7 +910,8 @@ public:
             }
             const Compiled* compiled = nullptr;
             try {
-                compiled = &kernel_for(sig, layout, dp.ranges ? (mode_ == V_GLOBAL ? V_GLOBAL_R : V_LDS_R) : mode_);
+                if (mode_ == V_GLOBAL && !dp.ranges) compiled = staged_kernel(sig, layout, dp.n - start_row);
+                if (!compiled) compiled = &kernel_for(sig, layout, dp.ranges ? (mode_ == V_GLOBAL ? V_GLOBAL_R : V_LDS_R) : mode_);
             }
             catch (const Error& e) {
                 // the group state may be too wide for the wave's / the workgroup's LDS budget: move on to the next tier
@@ -1080,7 +1081,68 @@ private:
         // 2: one overflowed.  An operator that finds 1 here does not cut a short probe launch off its first page and wait for it:
         // the whole page goes out and is confirmed late, like every later page (a wrong guess is the redo path of confirm_oldest).
         mutable std::atomic<int> lds_verdict{0};
+        // V_GLOBAL_S: what the first launch of this plan's staged kernel predicted -- 1: the staged loads move at most kStagedGain
+        // of the bytes the plain loop moves, the staged kernel stays; 2: they do not, the plain kernel takes over
+        mutable std::atomic<int> staged_verdict{0};
     };
+
+    // ---- staged loads (V_GLOBAL_S) ----
+    // PRESTO_AMD_STAGED=0 | 1 | auto (default): never / always (whenever the plan stages its loads) / as the first launch predicts.
+    // Under auto, launches of fewer than kStagedMinRows rows keep the plain kernel: the staged one is not worth a compilation there.
+    static constexpr int64_t kStagedMinRows = (int64_t)1 << 22;
+    static constexpr double kStagedGain = 0.85;
+    static int staged_mode()
+    {
+        const char* e = getenv("PRESTO_AMD_STAGED");
+        if (!e || !strcmp(e, "auto")) return 2;
+        return atoi(e) != 0 ? 1 : 0;
+    }
+    // the staged kernel for rows of this page, or null: the plain one
+    const Compiled* staged_kernel(const std::string& sig, const std::vector<ChannelLayout>& layout, int64_t rows)
+    {
+        const int m = staged_mode();
+        if (m == 0 || spec_.n_stages < 2 || staged_refused_ || (m == 2 && rows < kStagedMinRows)) return nullptr;
+        const Compiled* ck = nullptr;
+        try {
+            ck = &kernel_for(sig, layout, V_GLOBAL_S);
+        }
+        catch (const Error& e) {
+            if (e.code != PA_ERR_NOT_SUPPORTED) throw;
+            staged_refused_ = true;  // (column types the staged loop does not load)
+            return nullptr;
+        }
+        return m == 2 && ck->staged_verdict.load(std::memory_order_relaxed) == 2 ? nullptr : ck;
+    }
+    // Bytes per row the staged loads are expected to move, from the rows alive in front of every stage, for independent rows in
+    // 128-byte lines: a line of stage k is fetched when one of its 128 / w_k rows is alive.
+    static double staged_bytes(const std::vector<int>& w, const std::vector<double>& alive)
+    {
+        double b = 0;
+        for (size_t k = 0; k < w.size(); k++) {
+            if (w[k] <= 0) continue;
+            const double p = k == 0 ? 1.0 : alive[k - 1];
+            b += w[k] * (1.0 - std::pow(1.0 - p, 128.0 / w[k]));
+        }
+        return b;
+    }
+    // after the first launch of the plan's staged kernel: keep it or go back to the plain one
+    void staged_decide(const Compiled& ck, const uint64_t* slab, int grid, int64_t vec_rows, hipStream_t s)
+    {
+        const KernelInfo& ki = ck.info;
+        const int ns = (int)ki.stage_bytes.size() - 1;
+        if (staged_mode() != 2 || ns < 1 || vec_rows <= 0 || ck.staged_verdict.load(std::memory_order_relaxed) != 0) return;
+        std::vector<uint64_t> cnt((size_t)grid * ns);
+        PA_HIP(hipMemcpyAsync(cnt.data(), slab + (size_t)grid * ki.nw, cnt.size() * 8, hipMemcpyDeviceToHost, s));
+        PA_HIP(hipStreamSynchronize(s));
+        std::vector<double> alive(ns, 0.0);
+        for (int b = 0; b < grid; b++) {
+            for (int k = 0; k < ns; k++) alive[k] += (double)cnt[(size_t)b * ns + k];
+        }
+        double eager = 0;
+        for (int k = 0; k < ns; k++) alive[k] /= (double)vec_rows;
+        for (int w : ki.stage_bytes) eager += w;
+        ck.staged_verdict.store(staged_bytes(ki.stage_bytes, alive) <= kStagedGain * eager ? 1 : 2, std::memory_order_relaxed);
+    }
     static std::shared_ptr<const Compiled> shared_lookup(const std::string& key)
     {
         std::lock_guard<std::mutex> lock(shared_mutex());
@@ -1686,7 +1748,9 @@ private:
             auto room_for_flush = [&](uint32_t r) { return ki.variant == V_LDSH ? (uint64_t)((grid + r - 1) / r) * (uint64_t)(ki.lc / 2) : (uint64_t)0; };
             uint64_t flush_room = room_for_flush(reps);
             if (ki.variant == V_GLOBAL) {
-                a.slab = static_cast<uint64_t*>(slab_.ensure((size_t)grid * ki.nw * 8));
+                // (a staged kernel counts its rows alive behind the partial states: staged_decide)
+                const size_t stage_words = ki.stage_bytes.empty() ? 0 : ki.stage_bytes.size() - 1;
+                a.slab = static_cast<uint64_t*>(slab_.ensure((size_t)grid * (ki.nw + stage_words) * 8));
                 if (!state_.ptr()) {
                     state_.ensure((size_t)ki.nw * 8);
                     PA_HIP(hipMemsetAsync(state_.ptr(), 0, (size_t)ki.nw * 8, s));
@@ -1759,6 +1823,7 @@ private:
             timer.end(s, !use_tail);
             if (ki.variant == V_GLOBAL) {
                 launch_merge_global_slab(a.slab, grid, ki.nw, ck.kinds.as<int32_t>(), state_.as<uint64_t>(), ctl_, s);
+                if (!ki.stage_bytes.empty()) staged_decide(ck, a.slab, grid, a.vec ? (n & ~(int64_t)3) : 0, s);
             }
             else if (ki.variant == V_LDS) {
                 // The merge skips itself when the launch overflowed (overflow_rows != 0).  It runs on the merge
@@ -1993,6 +2058,7 @@ private:
     std::string plan_fingerprint_;
     bool grouped_ = false, finishing_ = false, output_done_ = false, layout_fixed_ = false;
     int mode_ = V_GLOBAL, cus_ = 256, nw_ = 0, w_ = 0;
+    bool staged_refused_ = false;  // the plan stages its loads, but no staged kernel loads its columns
     std::string layout_id_;
     std::vector<bool> nullable_seen_;  // per channel: some page so far carried a valueIsNull array
     bool out_partial_ = false;         // the output is the accumulator states (Step.PARTIAL, or a generation to be combined)

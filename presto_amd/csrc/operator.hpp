@@ -100,6 +100,8 @@ void page_buffer_free(pa_page_buffer* buffer);
 // code-object source for a fused descriptor under the "no nulls, aligned" layout; used by build() to
 // pre-compile the TPC-H shapes and by the CPU-side codegen tests
 std::string fused_source_for_desc(const pa_fused_aggregation_desc* desc, int variant, std::string* entry);
+// the staged-load plan of a descriptor: per channel its stage (-1: not read); returns the number of stages
+int fused_stages_for_desc(const pa_fused_aggregation_desc* desc, int32_t* channel_stage, int32_t n);
 // ... under any nullability signature (bit c: channel c carries NULL flags) and for every tier
 std::string fused_source_for_layout(const pa_fused_aggregation_desc* desc, int variant, uint64_t nullable_channels);
 void lookup_source_shape_for_desc(const pa_hash_builder_desc* build, pa_lookup_source* bridge);

@@ -142,6 +142,7 @@ bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layo
     for (int c = 0; c < s.n_in; c++) {
         if (!s.used[c]) continue;
         const std::string C = std::to_string(c);
+        const size_t first = vars.size();
         switch (layout[c].type) {
             case PA_BIGINT:
             case PA_DECIMAL:
@@ -159,6 +160,7 @@ bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layo
             default: return false;
         }
         if (layout[c].nullable) vars.push_back(VectorVar{"u32", "N" + C, nm.nl(c), 1, 0, true});
+        for (size_t i = first; i < vars.size(); i++) vars[i].channel = c;
     }
     return true;
 }
@@ -166,23 +168,29 @@ bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layo
 // (the argument list emit_vector_loads builds for row r of the quad, over variables with a prefix)
 std::string vector_var_args(const RowInputs& s, const std::vector<ChannelLayout>& layout, const std::string& P, int r)
 {
-    static const char* xyzw[4] = {"x", "y", "z", "w"};
     std::string a;
     for (int c = 0; c < s.n_in; c++) {
-        if (!s.used[c]) continue;
-        const std::string C = std::to_string(c);
-        switch (layout[c].type) {
-            case PA_BIGINT:
-            case PA_DECIMAL:
-            case PA_DOUBLE: a += ", " + P + std::string(r < 2 ? "A" : "B") + C + "." + xyzw[r & 1]; break;
-            case PA_INTEGER:
-            case PA_DATE: a += ", (i64)" + P + "A" + C + "." + xyzw[r]; break;
-            case PA_REAL: a += ", " + P + "A" + C + "." + xyzw[r]; break;
-            case PA_BOOLEAN: a += ", ((" + P + "A" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u"; break;
-            default: throw Error(PA_ERR_NOT_SUPPORTED, "column type not supported on device");
-        }
-        if (layout[c].nullable) a += ", ((" + P + "N" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
+        if (s.used[c]) a += vector_var_channel_args(layout, P, r, c);
     }
+    return a;
+}
+
+std::string vector_var_channel_args(const std::vector<ChannelLayout>& layout, const std::string& P, int r, int c)
+{
+    static const char* xyzw[4] = {"x", "y", "z", "w"};
+    std::string a;
+    const std::string C = std::to_string(c);
+    switch (layout[c].type) {
+        case PA_BIGINT:
+        case PA_DECIMAL:
+        case PA_DOUBLE: a += ", " + P + std::string(r < 2 ? "A" : "B") + C + "." + xyzw[r & 1]; break;
+        case PA_INTEGER:
+        case PA_DATE: a += ", (i64)" + P + "A" + C + "." + xyzw[r]; break;
+        case PA_REAL: a += ", " + P + "A" + C + "." + xyzw[r]; break;
+        case PA_BOOLEAN: a += ", ((" + P + "A" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u"; break;
+        default: throw Error(PA_ERR_NOT_SUPPORTED, "column type not supported on device");
+    }
+    if (layout[c].nullable) a += ", ((" + P + "N" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
     return a;
 }
 

@@ -41,10 +41,13 @@ struct VectorVar {
     int per_quad;                    // 2: the variable holds half a quad (index 2 q + half), 1: the whole quad
     int half;
     bool maybe_null;                 // (a valueIsNull array that a page may leave out)
+    int channel = -1;
     std::string load(const std::string& q) const;
 };
 bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::vector<VectorVar>& vars, const ColumnNames& names = ColumnNames());
 std::string vector_var_args(const RowInputs& s, const std::vector<ChannelLayout>& layout, const std::string& prefix, int r);
+// the part of that list that is channel c's
+std::string vector_var_channel_args(const std::vector<ChannelLayout>& layout, const std::string& prefix, int r, int c);
 // the same with the loads of the row's values named: declarations of locals <name><suffix> go to `decl` (so that the loads of several
 // rows can be issued before the first row is worked on), the returned argument list names them
 std::string scalar_loads(const RowInputs& s, const std::vector<ChannelLayout>& layout, const std::string& row, const std::string& suffix,
