@@ -373,6 +373,40 @@ typedef struct pa_lookup_join_desc {
     const pa_expr* filter;
 } pa_lookup_join_desc;
 
+/* SetBuilderOperator + HashSemiJoinOperator: `x [NOT] IN (SELECT y ...)`, planned as a SemiJoinNode by
+ * LocalExecutionPlanner.visitSemiJoin (LocalExecutionPlanner.java:2749-2835; SetBuilderOperator.java, ChannelSet.java,
+ * HashSemiJoinOperator.java:168-221).  The set is built over one channel of the build pages; the probe operator's output page is
+ * its input page with one BOOLEAN column appended (Page.appendColumn), the mark of each row's key k (HashSemiJoinOperator.java:190-218):
+ *   k NULL,     set without positions                 -> false
+ *   k NULL,     set with positions                    -> NULL
+ *   k not NULL, k in the set                          -> true
+ *   k not NULL, k not in the set, set holds a NULL    -> NULL
+ *   k not NULL, k not in the set, no NULL in the set  -> false
+ * Membership is IS NOT DISTINCT FROM (ChannelSet.contains -> GroupByHash.contains): every NaN matches every NaN and -0.0 matches
+ * +0.0 (DOUBLE, REAL), VARCHAR compares bytes whatever its VARCHAR(n) bound, any non-zero BOOLEAN byte is true.  Key types: BIGINT,
+ * INTEGER, DATE, DOUBLE, REAL, BOOLEAN, VARCHAR, PA_DECIMAL; build and probe key types must be equal (PA_ERR_INVALID_ARGUMENT),
+ * PA_LONG_DECIMAL / PA_ROW are PA_ERR_NOT_SUPPORTED.  $hashvalue channels (hash_channel, probe_hash_channel) are accepted and change
+ * no result.  A row's mark depends on that row alone: not on page boundaries, nor on the order of the build pages. */
+typedef struct pa_set_builder_desc {     /* SetBuilderOperatorFactory(setChannel, hashChannel, expectedPositions) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere: VARCHAR(n) bound / PA_DECIMAL_PARAM; NULL = all 0 */
+    int32_t set_channel;
+    int32_t hash_channel;                /* or -1 */
+    int32_t expected_positions;
+    void* stream;
+} pa_set_builder_desc;
+
+typedef struct pa_hash_semi_join_desc {  /* HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel) */
+    int32_t probe_channel_count;
+    const int32_t* probe_types;
+    const int32_t* probe_type_params;    /* may be NULL */
+    int32_t probe_join_channel;
+    int32_t probe_hash_channel;          /* or -1 */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_hash_semi_join_desc;
+
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
  * factories in one Driver).  Semantically the composition of the three descriptors: the join's probe page is the projection
@@ -466,6 +500,7 @@ typedef struct pa_domain {
 
 typedef struct pa_operator pa_operator;             /* opaque operator handle */
 typedef struct pa_lookup_source pa_lookup_source;   /* opaque: JoinBridge / LookupSourceFactory */
+typedef struct pa_channel_set pa_channel_set;       /* opaque: SetBuilderOperator.SetSupplier (the ChannelSet of a semi-join) */
 
 /* ---- library lifecycle ---- */
 int32_t pa_abi_version(void);
@@ -577,6 +612,19 @@ int32_t pa_lookup_join_create(const pa_lookup_join_desc* desc, pa_lookup_source*
  * channels (OuterLookupSource.java:120-160).  desc->join_type must be LOOKUP_OUTER or FULL_OUTER, as for the probe operators
  * of the same bridge (they mark the visited positions). */
 int32_t pa_lookup_outer_create(const pa_lookup_join_desc* desc, pa_lookup_source* bridge, pa_operator** out);
+/* Semi-join (pa_set_builder_desc above).  The set handle, its builder and its probe operators may be closed / destroyed in any order.
+ * Set builder: needs input until finish, which publishes the set; one builder per set (a second: PA_ERR_ILLEGAL_STATE).  Probe
+ * operator: pa_op_is_blocked 1 and needs_input 0 until the set is published (add_input before: PA_ERR_ILLEGAL_STATE); then one output
+ * page per non-empty input page.  Several probe operators may share one set.  A PA_MEM_DEVICE input page given to a PA_MEM_DEVICE
+ * operator comes out with its own blocks and encodings (zero copy) and a new BOOLEAN block of 1 byte per row, whose nulls are set
+ * only when some mark is NULL. */
+int32_t pa_channel_set_create(pa_channel_set** out);
+int32_t pa_channel_set_destroy(pa_channel_set* set);
+/* ChannelSet.size() (distinct values; NULL counted as one, every NaN as one, -0.0 and +0.0 as one) and containsNull();
+ * PA_ERR_ILLEGAL_STATE before the builder finished */
+int32_t pa_channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
+int32_t pa_set_builder_create(const pa_set_builder_desc* desc, pa_channel_set* set, pa_operator** out);
+int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_set* set, pa_operator** out);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

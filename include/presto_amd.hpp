@@ -386,6 +386,71 @@ inline std::unique_ptr<Operator> createHashBuilderOperator(LookupSourceFactory& 
     return std::make_unique<Operator>(h);
 }
 
+// SetBuilderOperator.SetSupplier: the ChannelSet of a semi-join, shared by its SetBuilderOperator and its HashSemiJoinOperators
+class ChannelSetSupplier {
+public:
+    ChannelSetSupplier() { check(pa_channel_set_create(&h_)); }
+    ChannelSetSupplier(const ChannelSetSupplier&) = delete;
+    ChannelSetSupplier& operator=(const ChannelSetSupplier&) = delete;
+    ~ChannelSetSupplier()
+    {
+        if (h_) pa_channel_set_destroy(h_);
+    }
+    pa_channel_set* handle() { return h_; }
+    // ChannelSet.size() (NULL counted as one value) of the built set
+    int64_t size()
+    {
+        int64_t n = 0;
+        int32_t has_null = 0;
+        check(pa_channel_set_stats(h_, &n, &has_null));
+        return n;
+    }
+    bool containsNull()
+    {
+        int64_t n = 0;
+        int32_t has_null = 0;
+        check(pa_channel_set_stats(h_, &n, &has_null));
+        return has_null != 0;
+    }
+
+private:
+    pa_channel_set* h_ = nullptr;
+};
+
+// SetBuilderOperatorFactory(setChannel, hashChannel, expectedPositions); typeParams: per channel, VARCHAR(n) bound / PA_DECIMAL_PARAM
+inline std::unique_ptr<Operator> createSetBuilderOperator(ChannelSetSupplier& set, const std::vector<int32_t>& inputTypes, int32_t setChannel,
+                                                          int32_t hashChannel = -1, int32_t expectedPositions = 0,
+                                                          const std::vector<int32_t>& typeParams = {})
+{
+    pa_set_builder_desc d{};
+    d.input_channel_count = (int32_t)inputTypes.size();
+    d.input_types = inputTypes.data();
+    d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.set_channel = setChannel;
+    d.hash_channel = hashChannel;
+    d.expected_positions = expectedPositions;
+    pa_operator* h = nullptr;
+    check(pa_set_builder_create(&d, set.handle(), &h));
+    return std::make_unique<Operator>(h);
+}
+
+// HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel): the probe page with a BOOLEAN mark
+inline std::unique_ptr<Operator> createHashSemiJoinOperator(ChannelSetSupplier& set, const std::vector<int32_t>& probeTypes, int32_t probeJoinChannel,
+                                                            int32_t probeHashChannel = -1, int32_t outputMem = PA_MEM_HOST,
+                                                            const std::vector<int32_t>& typeParams = {})
+{
+    pa_hash_semi_join_desc d{};
+    d.probe_channel_count = (int32_t)probeTypes.size();
+    d.probe_types = probeTypes.data();
+    d.probe_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.probe_join_channel = probeJoinChannel;
+    d.probe_hash_channel = probeHashChannel;
+    d.output_mem = outputMem;
+    pa_operator* h = nullptr;
+    check(pa_hash_semi_join_create(&d, set.handle(), &h));
+    return std::make_unique<Operator>(h);
+}
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

@@ -65,6 +65,13 @@ final class GpuNative
     static native long createFusedJoin(long bridge, int[] inputTypes, int[] typeParams, long filter, long[] projections, int[] projectionTypes,
             int[] probeJoinChannels, int[] probeOutputChannels, int[] joinedTypes, int[] groupByChannels, int step, int[] aggFns, int[] aggInputs,
             int[] aggMasks, int[] aggInputTypes, int expectedGroups, int outputMem);
+    /** SetBuilderOperator.SetSupplier: the pa_channel_set a semi-join's set builder and probe operators share (GpuSemiJoin). */
+    static native long channelSetCreate();
+    static native void channelSetDestroy(long channelSet);
+    /** SetBuilderOperatorFactory(setChannel, hashChannel, expectedPositions); typeParams may be null. */
+    static native long createSetBuilder(long channelSet, int[] inputTypes, int[] typeParams, int setChannel, int hashChannel, int expectedPositions);
+    /** HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel): the probe page plus a BOOLEAN mark. */
+    static native long createHashSemiJoin(long channelSet, int[] probeTypes, int[] typeParams, int probeJoinChannel, int probeHashChannel, int outputMem);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

@@ -23,9 +23,24 @@ public final class GpuOperatorFactory
     private final List<Type> inputTypes;
     private final List<Type> outputTypes;
     private final LongSupplier create;   // -> pa_operator* (throws GpuNativeException)
+    private final SharedHandle shared;   // a native handle `create` reads (a semi-join's channel set), or null
     private boolean closed;
 
+    /** A native handle several factories read: released (destroyed) when the last of them had noMoreOperators. */
+    interface SharedHandle
+    {
+        void retain();
+
+        void release();
+    }
+
     GpuOperatorFactory(int operatorId, PlanNodeId planNodeId, String operatorType, List<Type> inputTypes, List<Type> outputTypes, LongSupplier create)
+    {
+        this(operatorId, planNodeId, operatorType, inputTypes, outputTypes, create, null);
+    }
+
+    GpuOperatorFactory(int operatorId, PlanNodeId planNodeId, String operatorType, List<Type> inputTypes, List<Type> outputTypes, LongSupplier create,
+            SharedHandle shared)
     {
         this.operatorId = operatorId;
         this.planNodeId = planNodeId;
@@ -33,6 +48,10 @@ public final class GpuOperatorFactory
         this.inputTypes = inputTypes;
         this.outputTypes = outputTypes;
         this.create = create;
+        this.shared = shared;
+        if (shared != null) {
+            shared.retain();
+        }
     }
 
     @Override
@@ -48,12 +67,15 @@ public final class GpuOperatorFactory
     @Override
     public void noMoreOperators()
     {
+        if (!closed && shared != null) {
+            shared.release();   // (operators created so far hold what they need of it natively)
+        }
         closed = true;
     }
 
     @Override
     public OperatorFactory duplicate()
     {
-        return new GpuOperatorFactory(operatorId, planNodeId, operatorType, inputTypes, outputTypes, create);
+        return new GpuOperatorFactory(operatorId, planNodeId, operatorType, inputTypes, outputTypes, create, shared);
     }
 }

@@ -499,6 +499,51 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createHashBuilder(JNIEnv* en
     return (jlong)(intptr_t)op;
 }
 
+/* LocalExecutionPlanner.visitSemiJoin: SetBuilderOperatorFactory + HashSemiJoinOperator.createOperatorFactory sharing one
+ * pa_channel_set (the SetSupplier).  typeParams may be null (all 0) or one VARCHAR(n) bound / PA_DECIMAL_PARAM per channel. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_channelSetCreate(JNIEnv* env, jclass c)
+{
+    pa_channel_set* set = 0;
+    int32_t rc = pa_channel_set_create(&set);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)set;
+}
+JNIEXPORT void JNICALL Java_io_trino_gpu_GpuNative_channelSetDestroy(JNIEnv* env, jclass c, jlong h) { CHECK(pa_channel_set_destroy((pa_channel_set*)(intptr_t)h)); }
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createSetBuilder(JNIEnv* env, jclass c, jlong set, jintArray inputTypes, jintArray typeParams,
+        jint setChannel, jint hashChannel, jint expectedPositions)
+{
+    jsize n, np_ = 0;
+    pa_set_builder_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t* types = ints_of(env, inputTypes, &n);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.set_channel = setChannel; d.hash_channel = hashChannel; d.expected_positions = expectedPositions;
+    pa_operator* op = 0;
+    int32_t rc = pa_set_builder_create(&d, (pa_channel_set*)(intptr_t)set, &op);
+    free(params); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createHashSemiJoin(JNIEnv* env, jclass c, jlong set, jintArray probeTypes, jintArray typeParams,
+        jint probeJoinChannel, jint probeHashChannel, jint outputMem)
+{
+    jsize n, np_ = 0;
+    pa_hash_semi_join_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t* types = ints_of(env, probeTypes, &n);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.probe_channel_count = n; d.probe_types = types; d.probe_type_params = params && np_ == n ? params : 0;
+    d.probe_join_channel = probeJoinChannel; d.probe_hash_channel = probeHashChannel; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_hash_semi_join_create(&d, (pa_channel_set*)(intptr_t)set, &op);
+    free(params); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

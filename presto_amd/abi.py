@@ -300,6 +300,30 @@ class pa_lookup_join_desc(C.Structure):
     ]
 
 
+class pa_set_builder_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("set_channel", C.c_int32),
+        ("hash_channel", C.c_int32),
+        ("expected_positions", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class pa_hash_semi_join_desc(C.Structure):
+    _fields_ = [
+        ("probe_channel_count", C.c_int32),
+        ("probe_types", C.POINTER(C.c_int32)),
+        ("probe_type_params", C.POINTER(C.c_int32)),
+        ("probe_join_channel", C.c_int32),
+        ("probe_hash_channel", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

@@ -572,6 +572,46 @@ int32_t pa_lookup_outer_create(const pa_lookup_join_desc* desc, pa_lookup_source
     });
 }
 
+// ---- semi-join ----
+int32_t pa_channel_set_create(pa_channel_set** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "out is null");
+        *out = channel_set_new();
+        return PA_OK;
+    });
+}
+int32_t pa_channel_set_destroy(pa_channel_set* set)
+{
+    return guarded([&]() -> int32_t {
+        if (set) channel_set_delete(set);
+        return PA_OK;
+    });
+}
+int32_t pa_channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null)
+{
+    return guarded([&]() -> int32_t {
+        channel_set_stats(set, size, contains_null);
+        return PA_OK;
+    });
+}
+int32_t pa_set_builder_create(const pa_set_builder_desc* desc, pa_channel_set* set, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr && set != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_set_builder(desc, set);
+        return PA_OK;
+    });
+}
+int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_set* set, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr && set != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_hash_semi_join(desc, set);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

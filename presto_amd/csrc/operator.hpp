@@ -63,6 +63,12 @@ pa_operator* make_lookup_join(const pa_lookup_join_desc* desc, pa_lookup_source*
 pa_operator* make_topn(const pa_topn_desc* desc);
 pa_operator* make_order_by(const pa_order_by_desc* desc);
 pa_operator* make_lookup_outer(const pa_lookup_join_desc* desc, pa_lookup_source* bridge);
+// semi-join (op_semi_join.cpp): the set handle, SetBuilderOperator and HashSemiJoinOperator
+pa_channel_set* channel_set_new();
+void channel_set_delete(pa_channel_set* set);
+void channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
+pa_operator* make_set_builder(const pa_set_builder_desc* desc, pa_channel_set* set);
+pa_operator* make_hash_semi_join(const pa_hash_semi_join_desc* desc, pa_channel_set* set);
 // the consumer of an aggregation's output is a TopN over it: groups that cannot be among its n best rows may be left out (op_fused.hpp);
 // false: the operator does not take the hint (it emits everything)
 bool aggregation_set_output_topn(pa_operator* op, int64_t n, const int32_t* sort_channels, const int32_t* sort_orders, int32_t count);

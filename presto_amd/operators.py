@@ -712,6 +712,83 @@ def LookupJoinOperator(bridge, probe_types, probe_join_channels, probe_output_ch
     return Operator(h, keep)
 
 
+# ---- semi-join -------------------------------------------------------------------------------------------
+class SetSupplier:
+    """SetBuilderOperator.SetSupplier: the ChannelSet a SetBuilderOperator builds and its HashSemiJoinOperators read
+    (…/operator/SetBuilderOperator.java, ChannelSet.java)."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        check(lib().pa_channel_set_create(C.byref(h)))
+        self._h = h
+
+    def stats(self):
+        """(ChannelSet.size(), ChannelSet.containsNull()) of the built set: NULL counts as one value, every NaN as one, -0.0 and +0.0
+        as one."""
+        size, has_null = C.c_int64(), C.c_int32()
+        check(lib().pa_channel_set_stats(self._h, C.byref(size), C.byref(has_null)))
+        return size.value, bool(has_null.value)
+
+    def destroy(self):
+        if self._h:
+            lib().pa_channel_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def SetBuilderOperatorFactory(input_types, set_channel, hash_channel=-1, expected_positions=0, stream=None, type_params=None):
+    """SetBuilderOperatorFactory(setChannel, hashChannel, expectedPositions) (…/operator/SetBuilderOperator.java)."""
+    d = abi.pa_set_builder_desc()
+    types = abi.int32_array(input_types)
+    keep = [types]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.set_channel = set_channel
+    d.hash_channel = hash_channel
+    d.expected_positions = expected_positions
+    d.stream = stream
+    return JoinOperatorFactory(lib().pa_set_builder_create, d, keep)
+
+
+def SetBuilderOperator(set_supplier, input_types, set_channel, hash_channel=-1, expected_positions=0, stream=None, type_params=None):
+    return SetBuilderOperatorFactory(input_types, set_channel, hash_channel, expected_positions, stream, type_params).createOperator(set_supplier)
+
+
+def HashSemiJoinOperatorFactory(probe_types, probe_join_channel, probe_hash_channel=-1, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel)
+    (…/operator/HashSemiJoinOperator.java:168-221): the output page is the probe page with a BOOLEAN mark column appended."""
+    d = abi.pa_hash_semi_join_desc()
+    types = abi.int32_array(probe_types)
+    keep = [types]
+    d.probe_channel_count = len(probe_types)
+    d.probe_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(probe_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.probe_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.probe_join_channel = probe_join_channel
+    d.probe_hash_channel = probe_hash_channel
+    d.output_mem = output_mem
+    d.stream = stream
+    return JoinOperatorFactory(lib().pa_hash_semi_join_create, d, keep)
+
+
+def HashSemiJoinOperator(set_supplier, probe_types, probe_join_channel, probe_hash_channel=-1, output_mem=abi.MEM_HOST, stream=None,
+                         type_params=None):
+    return HashSemiJoinOperatorFactory(probe_types, probe_join_channel, probe_hash_channel, output_mem, stream, type_params).createOperator(set_supplier)
+
+
 # ---- driver loop ---------------------------------------------------------------------------------------
 def to_pages(operator, input_pages):
     """OperatorAssertion.toPages (core/trino-main/src/test/java/io/trino/operator/OperatorAssertion.java:62-138):
