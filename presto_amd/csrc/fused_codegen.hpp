@@ -9,6 +9,8 @@
 //   fused_tier_gt.cpp      GT      the HBM table: upsert + atomics, thread-private run combining, spill lists
 //   fused_tier_probe.cpp   the probe stage in front of any tier (pa_pre / pa_post, lazy channels, four probes per quad) and BROW,
 //                          the tier whose table slot is the build position
+// The host side that launches a tier's kernels is the launcher of its family in op_fused_launch.cpp (launch_global, launch_lds,
+// launch_table for LDSH / LDSP / GT, run_page_build_rows for BROW; HASH: run_page_partitioned, op_fused_table.cpp).
 // A tier's file holds the text only that tier's kernels contain; tests/test_codegen_tiers.py compiles every tier x nullability
 // signature x key layout for gfx950 without a GPU, scripts/dump_codegen.py writes the sources out (a refactoring changes none).
 #pragma once

@@ -150,7 +150,7 @@ struct KernelInfo {
     int variant = V_GLOBAL;
     bool ranged = false;  // the kernel walks a table of row ranges (V_GLOBAL_R / V_LDS_R; `variant` names the base variant)
     // V_GLOBAL_S: bytes per row each stage loads (values and NULL flags); the kernel writes, per workgroup, the rows that asked for
-    // the columns of stage 1 .. n - 1 into slab words gridDim.x * nw + blockIdx.x * (n - 1) + k - 1 (the decision: op_fused.hpp)
+    // the columns of stage 1 .. n - 1 into slab words gridDim.x * nw + blockIdx.x * (n - 1) + k - 1 (the decision: op_fused_kernels.cpp, staged_decide)
     std::vector<int> stage_bytes;
     int nw = 0, w = 0, c = 0, block = 256;
     int lc = 0;  // V_LDSH: slots of the workgroup's LDS table

@@ -86,9 +86,9 @@ void FusedAggregationOperator::rerank_words(int c, const uint32_t* ranks, hipStr
         const bool is_min = ag.fn == PA_AGG_MIN;
         if (vw < 0 || !done.insert({vw, is_min}).second) continue;
         if (grouped_) {
-            if (gt_cap_ == 0 || gt_words_.ptr() == nullptr) continue;
-            for (uint32_t r = 0; r < gt_rep_; r++) {
-                launch_rerank_words(gt_words_.as<uint64_t>() + ((uint64_t)r * nw_ + (uint64_t)vw) * gt_cap_, (int64_t)gt_cap_, is_min, ranks, s);
+            if (gt_.cap == 0 || gt_.words.ptr() == nullptr) continue;
+            for (uint32_t r = 0; r < gt_.rep; r++) {
+                launch_rerank_words(gt_.words.as<uint64_t>() + ((uint64_t)r * nw_ + (uint64_t)vw) * gt_.cap, (int64_t)gt_.cap, is_min, ranks, s);
             }
         }
         else if (state_.ptr() != nullptr) {
@@ -180,6 +180,24 @@ void FusedAggregationOperator::decode_interned_keys()
         oc.varwidth = true;
         oc.host_ready = false;
     }
+}
+
+// channel of the page projection `proj` names when min / max go through its rank (Spec::ranked), else -1
+int FusedAggregationOperator::ranked_channel(int proj) const
+{
+    const OwnedExpr& pe = spec_.proj[(size_t)proj];
+    if (!pe.is_input_ref()) return -1;
+    const int c = pe.node(pe.root).channel;
+    return c >= 0 && c < spec_.n_in && spec_.ranked[c] ? c : -1;
+}
+
+// channel of group key gi when that channel is interned, else -1
+int FusedAggregationOperator::interned_channel(int gi) const
+{
+    const OwnedExpr& pe = spec_.proj[spec_.group_proj[gi]];
+    if (!pe.is_input_ref()) return -1;
+    const int c = pe.node(pe.root).channel;
+    return c < spec_.n_in && spec_.interned[c] ? c : -1;  // (channels >= n_in: build columns of the probe stage)
 }
 
 }  // namespace fused_op

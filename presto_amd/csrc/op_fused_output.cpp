@@ -1,6 +1,12 @@
 // op_fused_output.cpp -- FusedAggregationOperator (op_fused.hpp): the result page -- groups emitted on the device (k_gt_emit), or a few
 // groups assembled on the host.
+#include <algorithm>
+#include <cstring>
+
+#include "decimal_host.hpp"
+#include "host_hash.hpp"
 #include "op_fused.hpp"
+#include "topn_kernels.hpp"
 
 namespace pa {
 namespace fused_op {
@@ -121,10 +127,10 @@ bool FusedAggregationOperator::emit_on_device(const KernelInfo& ki, int64_t grou
         a.col[c].nulls = nullable[c] ? static_cast<uint8_t*>(oc.nulls.ensure((size_t)groups)) : nullptr;
     }
     a.tag = table_tags();
-    a.keys = gt_keys_.as<uint64_t>();
+    a.keys = gt_.keys.as<uint64_t>();
     a.words = table_words();
     a.st = table_strides();
-    a.cap = gt_cap_;
+    a.cap = gt_.cap;
     a.W = std::max(w_, 1);
     a.NW = nw_;
     a.ncols = n;
@@ -139,7 +145,7 @@ bool FusedAggregationOperator::emit_on_device(const KernelInfo& ki, int64_t grou
     bool bounded = false;
     if (topn_hint_.n > 0 && !partial && groups >= (int64_t)1 << 16 && groups >= 64 * topn_hint_.n) {
         const int c0 = topn_hint_.channels[0];
-        const int64_t cap = (int64_t)gt_cap_;
+        const int64_t cap = (int64_t)gt_.cap;
         constexpr int64_t kSample = (int64_t)1 << 14;
         const double j = (double)topn_hint_.n * (double)kSample / (double)cap;
         const int64_t rank = (int64_t)std::ceil(j + 8.0 + 4.0 * std::sqrt(j));
@@ -198,12 +204,12 @@ void FusedAggregationOperator::build_output()
     const KernelInfo& ki = compiled_.begin()->second->info;
 
     // the error word and, for grouped results, the dense (keys, words) rows of the occupied table slots
-    const bool sub_tables = grouped_ && sub_parts_ > 0;
+    const bool sub_tables = grouped_ && ldsp_.parts > 0;
     const int32_t* per_part = nullptr;
     if (sub_tables) {
         // (the partitions' group counts, the table's and the error word in ONE round trip)
-        per_part = static_cast<const int32_t*>(h_parts_.ensure((size_t)sub_parts_ * 4));
-        PA_HIP(hipMemcpyAsync(h_parts_.ptr(), sub_count_.ptr(), (size_t)sub_parts_ * 4, hipMemcpyDeviceToHost, s));
+        per_part = static_cast<const int32_t*>(h_parts_.ensure((size_t)ldsp_.parts * 4));
+        PA_HIP(hipMemcpyAsync(h_parts_.ptr(), ldsp_.count.ptr(), (size_t)ldsp_.parts * 4, hipMemcpyDeviceToHost, s));
         read_group_counts(s);
     }
     else {
@@ -212,35 +218,35 @@ void FusedAggregationOperator::build_output()
     }
     raise_if(h_ctl_[0]);
     if (sub_tables) {
-        // Partition-owned tables.  Their HBM form IS a group table of sub_parts_ * lc slots (same arrays, same layouts; only the
+        // Partition-owned tables.  Their HBM form IS a group table of ldsp_.parts * lc slots (same arrays, same layouts; only the
         // probe sequence differs, and nothing probes any more).  When the HBM table proper holds no group -- nothing fell
         // through, no other tier ran -- they simply become the table; else their groups are folded into it, one upsert per group.
         uint64_t total = 0;
-        for (int p = 0; p < sub_parts_; p++) total += (uint64_t)per_part[p];
-        const uint32_t sub_cap = (uint32_t)sub_parts_ * (uint32_t)sub_lc_;
-        if (groups_sum_ == 0) {
-            gt_tag_ = std::move(sub_tag_);
-            gt_keys_ = std::move(sub_keys_);
-            gt_words_ = std::move(sub_words_);
-            gt_cap_ = sub_cap;
-            gt_rep_ = 1;
+        for (int p = 0; p < ldsp_.parts; p++) total += (uint64_t)per_part[p];
+        const uint32_t sub_cap = (uint32_t)ldsp_.parts * (uint32_t)ldsp_.lc;
+        if (gt_.groups_sum == 0) {
+            gt_.tag = std::move(ldsp_.tag);
+            gt_.keys = std::move(ldsp_.keys);
+            gt_.words = std::move(ldsp_.words);
+            gt_.cap = sub_cap;
+            gt_.rep = 1;
             // (the count goes to the device from the pinned control block: no wait)
             h_ctl_[1] = (int32_t)total;
             PA_HIP(hipMemcpyAsync(ctl_ + 1, h_ctl_ + 1, 4, hipMemcpyHostToDevice, s));
-            groups_upper_ = groups_sum_ = total;
+            gt_.groups_upper = gt_.groups_sum = total;
         }
         else {
-            ensure_table(groups_sum_ + total + 1024, 1);
-            launch_gt_fold(sub_tag_.as<uint64_t>(), sub_keys_.as<uint64_t>(), sub_words_.as<uint64_t>(), sub_cap, 1, std::max(w_, 1), nw_, kinds_dev_,
-                           gt_tag_.as<uint64_t>(), gt_keys_.as<uint64_t>(), gt_words_.as<uint64_t>(), gt_cap_ - 1, 1, ctl_ + 1, rep_count_.as<int32_t>(), ctl_, s);
+            ensure_table(gt_.groups_sum + total + 1024, 1);
+            launch_gt_fold(ldsp_.tag.as<uint64_t>(), ldsp_.keys.as<uint64_t>(), ldsp_.words.as<uint64_t>(), sub_cap, 1, std::max(w_, 1), nw_, kinds_dev_,
+                           gt_.tag.as<uint64_t>(), gt_.keys.as<uint64_t>(), gt_.words.as<uint64_t>(), gt_.cap - 1, 1, ctl_ + 1, gt_.rep_count.as<int32_t>(), ctl_, s);
             PA_HIP(hipMemcpyAsync(h_ctl_, ctl_, 32, hipMemcpyDeviceToHost, s));
             PA_HIP(hipStreamSynchronize(s));
             raise_if(h_ctl_[0]);
-            sub_tag_.release();
-            sub_keys_.release();
-            sub_words_.release();
+            ldsp_.tag.release();
+            ldsp_.keys.release();
+            ldsp_.words.release();
         }
-        sub_parts_ = 0;
+        ldsp_.parts = 0;
     }
     std::vector<uint64_t> keys, words;
     int64_t groups = 0;
@@ -249,17 +255,17 @@ void FusedAggregationOperator::build_output()
         words.assign(nw_, 0);
         if (state_.ptr()) PA_HIP(hipMemcpy(words.data(), state_.ptr(), (size_t)nw_ * 8, hipMemcpyDeviceToHost));
     }
-    else if (gt_cap_ > 0) {
-        if (gt_rep_ > 1) {
+    else if (gt_.cap > 0) {
+        if (gt_.rep > 1) {
             // fold the replicas into one table: states of one key combine with the aggregates' combine functions
             read_group_counts(s);
-            ensure_table(groups_sum_, 1);
+            ensure_table(gt_.groups_sum, 1);
             PA_HIP(hipMemcpyAsync(h_ctl_, ctl_, 32, hipMemcpyDeviceToHost, s));
             PA_HIP(hipStreamSynchronize(s));
             raise_if(h_ctl_[0]);
         }
         // build-row table of some size: the output blocks straight from the accumulators and the build columns
-        if (build_rows_table_ && (int64_t)gt_cap_ >= (1 << 14) && emit_on_device(ki, (int64_t)gt_cap_, true)) return;
+        if (build_rows_table_ && (int64_t)gt_.cap >= (1 << 14) && emit_on_device(ki, (int64_t)gt_.cap, true)) return;
         if (build_rows_table_) {
             // build-row table: no kernel counted its groups, and its key words are still to be written -- once per group, from
             // the build columns (pa_brow_keys)
@@ -269,12 +275,12 @@ void FusedAggregationOperator::build_output()
             a.err = ctl_;
             a.gt_count = ctl_ + 1;
             PA_HIP(hipMemsetAsync(ctl_ + 1, 0, 4, s));
-            a.gt_tag = gt_tag_.as<uint64_t>();
-            a.gt_keys = gt_keys_.as<uint64_t>();
-            a.gt_words = gt_words_.as<uint64_t>();
-            a.gt_mask = gt_cap_ - 1;
+            a.gt_tag = gt_.tag.as<uint64_t>();
+            a.gt_keys = gt_.keys.as<uint64_t>();
+            a.gt_words = gt_.words.as<uint64_t>();
+            a.gt_mask = gt_.cap - 1;
             void* params[] = {&a};
-            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)gt_cap_ + 255) / 256, (int64_t)cus_ * 8));
+            const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)gt_.cap + 255) / 256, (int64_t)cus_ * 8));
             PA_HIP(hipModuleLaunchKernel(brow_keys_->tail_kernel.fn, grid, 1, 1, 256, 1, 1, 0, s, params, nullptr));
             PA_HIP(hipMemcpyAsync(h_ctl_, ctl_, 32, hipMemcpyDeviceToHost, s));
             PA_HIP(hipStreamSynchronize(s));
@@ -288,7 +294,7 @@ void FusedAggregationOperator::build_output()
             dense_words_.ensure((size_t)groups * nw_ * 8);
             PA_HIP(hipMemsetAsync(ctl_ + 7, 0, 4, s));
             const GtStrides st = table_strides();
-            launch_gt_compact(table_tags(), gt_keys_.as<uint64_t>(), table_words(), gt_cap_, kw, nw_, dense_keys_.as<uint64_t>(),
+            launch_gt_compact(table_tags(), gt_.keys.as<uint64_t>(), table_words(), gt_.cap, kw, nw_, dense_keys_.as<uint64_t>(),
                               dense_words_.as<uint64_t>(), reinterpret_cast<uint32_t*>(ctl_ + 7), s, &st);
             uint8_t* land = static_cast<uint8_t*>(h_table_.ensure((size_t)groups * (kw + nw_) * 8));
             PA_HIP(hipMemcpyAsync(land, dense_keys_.ptr(), (size_t)groups * kw * 8, hipMemcpyDeviceToHost, s));

@@ -91,5 +91,18 @@ void launch_gt_emit_keys(const GtEmitArgs& args, int column, int sort_order, uin
 void launch_gt_emit_keys_strided(const GtEmitArgs& args, int column, int sort_order, int64_t stride, int64_t count, uint64_t* keys, hipStream_t s);
 // out[i] = in[0] + ... + in[i - 1] for i in [0, n], n <= 5119 (static_kernels.hip)
 void launch_exclusive_prefix_i64(const int64_t* in, int32_t n, int64_t* out, hipStream_t s);
+void launch_fill_u64(uint64_t* dst, uint64_t value, int64_t n, hipStream_t s);
+
+// the fused aggregation operator's merges (op_fused_launch.cpp) and its group table's upkeep (op_fused_table.cpp, op_fused_output.cpp)
+void launch_merge_global_slab(const uint64_t* slab, int blocks, int nw, const int32_t* kinds_dev, uint64_t* state, int32_t* err,
+                              hipStream_t s);
+void launch_merge_lds_slab(const uint64_t* slab, int waves, int c, int w, int nw, const int32_t* kinds_dev, uint64_t* gt_tag,
+                           uint64_t* gt_keys, uint64_t* gt_words, uint32_t gt_mask, int32_t gt_max_fill, int32_t* gt_count,
+                           int32_t* err, const uint64_t* overflow_rows, int32_t* entry_slot, hipStream_t s);
+void launch_gt_fold(const uint64_t* old_tag, const uint64_t* old_keys, const uint64_t* old_words, uint32_t old_cap, uint32_t old_reps, int w,
+                    int nw, const int32_t* kinds_dev, uint64_t* tag, uint64_t* keys, uint64_t* words, uint32_t mask, uint32_t new_reps,
+                    int32_t* count0, int32_t* rep_count, int32_t* err, hipStream_t s);
+void launch_gt_compact(const uint64_t* tag, const uint64_t* keys, const uint64_t* words, uint32_t cap, int w, int nw, uint64_t* out_keys,
+                       uint64_t* out_words, uint32_t* counter, hipStream_t s, const GtStrides* strides = nullptr);
 
 }  // namespace pa
