@@ -407,6 +407,49 @@ typedef struct pa_hash_semi_join_desc {  /* HashSemiJoinOperator.createOperatorF
     void* stream;
 } pa_hash_semi_join_desc;
 
+/* MarkDistinctOperator + DistinctLimitOperator: `count(DISTINCT x)` / `SELECT DISTINCT ... LIMIT n`, planned by
+ * LocalExecutionPlanner.visitMarkDistinct (:1540) and visitDistinctLimit (:1455) (MarkDistinctOperator.java, MarkDistinctHash.java:52-69,
+ * DistinctLimitOperator.java:175-223), both over GroupByHash.getGroupIds.  A row is NEW when no earlier row -- of an earlier page, or at
+ * a smaller position of the same page -- has a key that is not distinct from its own, over the operator's whole life; the result does
+ * not depend on how the input is cut into pages and is the same on every run.  Keys compare by IS NOT DISTINCT FROM over 1 .. 8
+ * distinct channels: NULL is one value per channel ((NULL, 1) and (NULL, 2) differ), every NaN is one value, -0.0 is +0.0 (DOUBLE, REAL),
+ * VARCHAR compares bytes, any non-zero BOOLEAN byte is true.  Key types: BIGINT, INTEGER, DATE, DOUBLE, REAL, BOOLEAN, VARCHAR,
+ * PA_DECIMAL; PA_LONG_DECIMAL / PA_ROW keys and more than 8 distinct channels are PA_ERR_NOT_SUPPORTED at creation.  hash_channel
+ * ($hashvalue) is validated and never read.
+ *   MarkDistinct: the output page is the input page with one BOOLEAN column appended (Page.appendColumn), true on NEW rows; it never
+ *     has nulls.  One output page per non-empty input page; needs_input is 0 while a page is pending; is_finished = finishing and
+ *     nothing pending.  A PA_MEM_DEVICE input page given to a PA_MEM_DEVICE operator comes out with its own blocks and encodings
+ *     (zero copy).
+ *   DistinctLimit: the output page holds the NEW rows' distinct channels in descriptor order, then the hash channel if there is one
+ *     (DistinctLimitOperator.java:76-79); only the first `limit` NEW rows of the operator's life are emitted, in arrival order.
+ *     needs_input = not finishing, fewer than `limit` rows emitted, nothing pending; is_finished = nothing pending and (finishing or
+ *     `limit` rows emitted): with limit 0, at creation.  A page without a NEW row produces no page.
+ * Empty input pages are accepted and produce nothing. */
+typedef struct pa_mark_distinct_desc {   /* MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere: VARCHAR(n) bound / PA_DECIMAL_PARAM; NULL = all 0 */
+    int32_t distinct_channel_count;
+    const int32_t* distinct_channels;
+    int32_t hash_channel;                /* or -1 */
+    int32_t expected_distinct;           /* first size of the table; 0 = the reference's 10 000 */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_mark_distinct_desc;
+
+typedef struct pa_distinct_limit_desc {  /* DistinctLimitOperatorFactory(sourceTypes, distinctChannels, limit, hashChannel) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* may be NULL */
+    int32_t distinct_channel_count;
+    const int32_t* distinct_channels;
+    int32_t hash_channel;                /* or -1 */
+    int32_t expected_distinct;           /* 0 = the reference's 10 000 */
+    int32_t output_mem;                  /* pa_mem */
+    int64_t limit;                       /* >= 0 */
+    void* stream;
+} pa_distinct_limit_desc;
+
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
  * factories in one Driver).  Semantically the composition of the three descriptors: the join's probe page is the projection
@@ -625,6 +668,13 @@ int32_t pa_channel_set_destroy(pa_channel_set* set);
 int32_t pa_channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
 int32_t pa_set_builder_create(const pa_set_builder_desc* desc, pa_channel_set* set, pa_operator** out);
 int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_set* set, pa_operator** out);
+/* MarkDistinct / DistinctLimit (pa_mark_distinct_desc above). */
+int32_t pa_mark_distinct_create(const pa_mark_distinct_desc* desc, pa_operator** out);
+int32_t pa_distinct_limit_create(const pa_distinct_limit_desc* desc, pa_operator** out);
+/* The counterpart of GroupByHash.getGroupCount() / getCapacity() for an operator made by the two entries above: *distinct_count = the
+ * keys seen so far (nextDistinctId; waits for the pages in flight), *table_capacity = slots of the table (a power of two).  Either
+ * pointer may be NULL.  Any other operator: PA_ERR_INVALID_ARGUMENT. */
+int32_t pa_distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* table_capacity);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

@@ -451,6 +451,54 @@ inline std::unique_ptr<Operator> createHashSemiJoinOperator(ChannelSetSupplier& 
     return std::make_unique<Operator>(h);
 }
 
+// MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel): the input page with a BOOLEAN column appended, true on
+// the first row that carries a key
+inline std::unique_ptr<Operator> createMarkDistinctOperator(const std::vector<int32_t>& inputTypes, const std::vector<int32_t>& distinctChannels,
+                                                            int32_t hashChannel = -1, int32_t expectedDistinct = 0, int32_t outputMem = PA_MEM_HOST,
+                                                            const std::vector<int32_t>& typeParams = {})
+{
+    pa_mark_distinct_desc d{};
+    d.input_channel_count = (int32_t)inputTypes.size();
+    d.input_types = inputTypes.data();
+    d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.distinct_channel_count = (int32_t)distinctChannels.size();
+    d.distinct_channels = distinctChannels.data();
+    d.hash_channel = hashChannel;
+    d.expected_distinct = expectedDistinct;
+    d.output_mem = outputMem;
+    pa_operator* h = nullptr;
+    check(pa_mark_distinct_create(&d, &h));
+    return std::make_unique<Operator>(h);
+}
+
+// DistinctLimitOperatorFactory(sourceTypes, distinctChannels, limit, hashChannel): the first `limit` distinct keys in arrival order
+inline std::unique_ptr<Operator> createDistinctLimitOperator(const std::vector<int32_t>& inputTypes, const std::vector<int32_t>& distinctChannels,
+                                                             int64_t limit, int32_t hashChannel = -1, int32_t expectedDistinct = 0,
+                                                             int32_t outputMem = PA_MEM_HOST, const std::vector<int32_t>& typeParams = {})
+{
+    pa_distinct_limit_desc d{};
+    d.input_channel_count = (int32_t)inputTypes.size();
+    d.input_types = inputTypes.data();
+    d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.distinct_channel_count = (int32_t)distinctChannels.size();
+    d.distinct_channels = distinctChannels.data();
+    d.hash_channel = hashChannel;
+    d.expected_distinct = expectedDistinct;
+    d.output_mem = outputMem;
+    d.limit = limit;
+    pa_operator* h = nullptr;
+    check(pa_distinct_limit_create(&d, &h));
+    return std::make_unique<Operator>(h);
+}
+
+// keys seen so far (nextDistinctId) of a MarkDistinct / DistinctLimit operator
+inline int64_t distinctCount(Operator& op)
+{
+    int64_t n = 0;
+    check(pa_distinct_stats(op.handle(), &n, nullptr));
+    return n;
+}
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

@@ -72,6 +72,12 @@ final class GpuNative
     static native long createSetBuilder(long channelSet, int[] inputTypes, int[] typeParams, int setChannel, int hashChannel, int expectedPositions);
     /** HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel): the probe page plus a BOOLEAN mark. */
     static native long createHashSemiJoin(long channelSet, int[] probeTypes, int[] typeParams, int probeJoinChannel, int probeHashChannel, int outputMem);
+    /** MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel): the input page plus a BOOLEAN mark (GpuDistinct). */
+    static native long createMarkDistinct(int[] inputTypes, int[] typeParams, int[] distinctChannels, int hashChannel, int expectedDistinct, int outputMem);
+    /** DistinctLimitOperatorFactory(sourceTypes, distinctChannels, limit, hashChannel): the first `limit` distinct keys in arrival order. */
+    static native long createDistinctLimit(int[] inputTypes, int[] typeParams, int[] distinctChannels, long limit, int hashChannel, int expectedDistinct, int outputMem);
+    /** {distinct keys seen so far, slots of the table} of a MarkDistinct / DistinctLimit operator (GroupByHash.getGroupCount / getCapacity). */
+    static native long[] distinctStats(long operator);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

@@ -544,6 +544,56 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createHashSemiJoin(JNIEnv* e
     return (jlong)(intptr_t)op;
 }
 
+/* LocalExecutionPlanner.visitMarkDistinct / visitDistinctLimit: MarkDistinctOperatorFactory / DistinctLimitOperatorFactory.  typeParams
+ * may be null (all 0) or one VARCHAR(n) bound / PA_DECIMAL_PARAM per channel. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createMarkDistinct(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,
+        jintArray distinctChannels, jint hashChannel, jint expectedDistinct, jint outputMem)
+{
+    jsize n, nd, np_ = 0;
+    pa_mark_distinct_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *dc = ints_of(env, distinctChannels, &nd);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.distinct_channel_count = nd; d.distinct_channels = dc; d.hash_channel = hashChannel; d.expected_distinct = expectedDistinct;
+    d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_mark_distinct_create(&d, &op);
+    free(params); free(dc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createDistinctLimit(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,
+        jintArray distinctChannels, jlong limit, jint hashChannel, jint expectedDistinct, jint outputMem)
+{
+    jsize n, nd, np_ = 0;
+    pa_distinct_limit_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *dc = ints_of(env, distinctChannels, &nd);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.distinct_channel_count = nd; d.distinct_channels = dc; d.hash_channel = hashChannel; d.expected_distinct = expectedDistinct;
+    d.output_mem = outputMem; d.limit = limit;
+    pa_operator* op = 0;
+    int32_t rc = pa_distinct_limit_create(&d, &op);
+    free(params); free(dc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+/* {distinct keys seen so far (nextDistinctId), slots of the table} of an operator made by the two natives above */
+JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_distinctStats(JNIEnv* env, jclass c, jlong op)
+{
+    int64_t count = 0, capacity = 0;
+    int32_t rc = pa_distinct_stats((pa_operator*)(intptr_t)op, &count, &capacity);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    jlong v[2] = {(jlong)count, (jlong)capacity};
+    jlongArray out = (*env)->NewLongArray(env, 2);
+    if (out) (*env)->SetLongArrayRegion(env, out, 0, 2, v);
+    return out;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

@@ -61,6 +61,9 @@ def lib():
     L.pa_channel_set_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.pa_set_builder_create.argtypes = [C.POINTER(abi.pa_set_builder_desc), vp, C.POINTER(vp)]
     L.pa_hash_semi_join_create.argtypes = [C.POINTER(abi.pa_hash_semi_join_desc), vp, C.POINTER(vp)]
+    L.pa_mark_distinct_create.argtypes = [C.POINTER(abi.pa_mark_distinct_desc), C.POINTER(vp)]
+    L.pa_distinct_limit_create.argtypes = [C.POINTER(abi.pa_distinct_limit_desc), C.POINTER(vp)]
+    L.pa_distinct_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pa_fused_join_aggregation_create.argtypes = [C.POINTER(abi.pa_fused_join_aggregation_desc), vp, C.POINTER(vp)]
     L.pa_fused_join_create.argtypes = [C.POINTER(abi.pa_fused_join_desc), vp, C.POINTER(vp)]
     L.pa_codegen_fused_join.argtypes = [C.POINTER(abi.pa_fused_join_aggregation_desc), C.POINTER(abi.pa_hash_builder_desc), C.c_int32, C.c_char_p, C.c_int64]

@@ -324,6 +324,35 @@ class pa_hash_semi_join_desc(C.Structure):
     ]
 
 
+class pa_mark_distinct_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("distinct_channel_count", C.c_int32),
+        ("distinct_channels", C.POINTER(C.c_int32)),
+        ("hash_channel", C.c_int32),
+        ("expected_distinct", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class pa_distinct_limit_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("distinct_channel_count", C.c_int32),
+        ("distinct_channels", C.POINTER(C.c_int32)),
+        ("hash_channel", C.c_int32),
+        ("expected_distinct", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("limit", C.c_int64),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

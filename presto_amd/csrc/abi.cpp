@@ -612,6 +612,33 @@ int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_
     });
 }
 
+// ---- MarkDistinct / DistinctLimit ----
+int32_t pa_mark_distinct_create(const pa_mark_distinct_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_mark_distinct(desc);
+        return PA_OK;
+    });
+}
+int32_t pa_distinct_limit_create(const pa_distinct_limit_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_distinct_limit(desc);
+        return PA_OK;
+    });
+}
+int32_t pa_distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* table_capacity)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(op != nullptr, PA_ERR_INVALID_ARGUMENT, "operator is null");
+        OpScope scope(op);
+        distinct_stats(op, distinct_count, table_capacity);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

@@ -69,6 +69,10 @@ void channel_set_delete(pa_channel_set* set);
 void channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
 pa_operator* make_set_builder(const pa_set_builder_desc* desc, pa_channel_set* set);
 pa_operator* make_hash_semi_join(const pa_hash_semi_join_desc* desc, pa_channel_set* set);
+// MarkDistinctOperator / DistinctLimitOperator (op_distinct.cpp); distinct_stats: nextDistinctId and the table's slots
+pa_operator* make_mark_distinct(const pa_mark_distinct_desc* desc);
+pa_operator* make_distinct_limit(const pa_distinct_limit_desc* desc);
+void distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* table_capacity);
 // the consumer of an aggregation's output is a TopN over it: groups that cannot be among its n best rows may be left out (op_fused.cpp, op_fused_output.cpp);
 // false: the operator does not take the hint (it emits everything)
 bool aggregation_set_output_topn(pa_operator* op, int64_t n, const int32_t* sort_channels, const int32_t* sort_orders, int32_t count);

@@ -8,6 +8,7 @@
 
 #include "semi_join_kernels.hpp"
 #include "kernels/pa_device.h"
+#include "kernels/pa_canon.h"
 
 namespace pa {
 
@@ -17,27 +18,6 @@ static inline int semi_grid(int64_t work)
     if (g < 1) g = 1;
     if (g > 256 * 16) g = 256 * 16;
     return (int)g;
-}
-
-// IS NOT DISTINCT FROM as equality of 64-bit keys (semi_join_kernels.hpp)
-__device__ __forceinline__ u64 semi_canon_bits(i32 type, const void* values, i64 r)
-{
-    switch (type) {
-        case PA_INTEGER:
-        case PA_DATE: return (u64)(i64)((const i32*)values)[r];
-        case PA_BOOLEAN: return ((const u8*)values)[r] != 0 ? 1ULL : 0ULL;  // any non-zero byte is true
-        case PA_DOUBLE: {
-            const u64 b = ((const u64*)values)[r];
-            if ((b & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL) return 0x7ff8000000000000ULL;  // every NaN is one value (DoubleType.java:181-192)
-            return b == 0x8000000000000000ULL ? 0ULL : b;                                            // -0.0 is +0.0
-        }
-        case PA_REAL: {
-            const u32 b = ((const u32*)values)[r];
-            if ((b & 0x7fffffffu) > 0x7f800000u) return 0x7fc00000ULL;
-            return b == 0x80000000u ? 0ULL : (u64)b;
-        }
-        default: return ((const u64*)values)[r];  // BIGINT, short DECIMAL (the unscaled value)
-    }
 }
 
 __global__ __launch_bounds__(256) void k_semi_canon(JoinCol key, i32 n, u64* __restrict__ out, i32* __restrict__ any_null)

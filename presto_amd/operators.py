@@ -92,6 +92,12 @@ class Operator:
             return np.zeros(0, np.int32), np.zeros(0, np.int32)
         return (download(DeviceBuffer(p.value, 4 * n), np.int32, n), download(DeviceBuffer(b.value, 4 * n), np.int32, n))
 
+    def distinctStats(self):
+        """MarkDistinct / DistinctLimit only: (distinct keys seen so far -- nextDistinctId --, slots of the table)."""
+        count, capacity = C.c_int64(), C.c_int64()
+        check(lib().pa_distinct_stats(self._h, C.byref(count), C.byref(capacity)))
+        return count.value, capacity.value
+
     def setDynamicFilter(self, channel, lookup_source_factory):
         """FilterAndProject only, before the first page: drop the rows whose `channel` value matches no build key of the (built)
         join bridge -- the join's dynamic filter applied upstream of the probe.  True when the filter is active."""
@@ -787,6 +793,57 @@ def HashSemiJoinOperatorFactory(probe_types, probe_join_channel, probe_hash_chan
 def HashSemiJoinOperator(set_supplier, probe_types, probe_join_channel, probe_hash_channel=-1, output_mem=abi.MEM_HOST, stream=None,
                          type_params=None):
     return HashSemiJoinOperatorFactory(probe_types, probe_join_channel, probe_hash_channel, output_mem, stream, type_params).createOperator(set_supplier)
+
+
+# ---- DISTINCT ----------------------------------------------------------------------------------------------
+def _distinct_desc(d, input_types, distinct_channels, hash_channel, expected_distinct, output_mem, stream, type_params):
+    types = abi.int32_array(input_types)
+    dc = abi.int32_array(distinct_channels)
+    keep = [types, dc]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.distinct_channel_count = len(distinct_channels)
+    d.distinct_channels = C.cast(dc, C.POINTER(C.c_int32))
+    d.hash_channel = hash_channel
+    d.expected_distinct = expected_distinct
+    d.output_mem = output_mem
+    d.stream = stream
+    return keep
+
+
+def MarkDistinctOperatorFactory(input_types, distinct_channels, hash_channel=-1, expected_distinct=0, output_mem=abi.MEM_HOST, stream=None,
+                                type_params=None):
+    """MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel) (…/operator/MarkDistinctOperator.java): the output
+    page is the input page with a BOOLEAN column appended, true on the first row that carries a key."""
+    d = abi.pa_mark_distinct_desc()
+    keep = _distinct_desc(d, input_types, distinct_channels, hash_channel, expected_distinct, output_mem, stream, type_params)
+    return OperatorFactory(lib().pa_mark_distinct_create, d, keep)
+
+
+def MarkDistinctOperator(input_types, distinct_channels, hash_channel=-1, expected_distinct=0, output_mem=abi.MEM_HOST, stream=None,
+                         type_params=None):
+    return MarkDistinctOperatorFactory(input_types, distinct_channels, hash_channel, expected_distinct, output_mem, stream, type_params).createOperator()
+
+
+def DistinctLimitOperatorFactory(input_types, distinct_channels, limit, hash_channel=-1, expected_distinct=0, output_mem=abi.MEM_HOST,
+                                 stream=None, type_params=None):
+    """DistinctLimitOperatorFactory(sourceTypes, distinctChannels, limit, hashChannel) (…/operator/DistinctLimitOperator.java): the
+    first `limit` distinct keys in arrival order; output = the distinct channels, then the hash channel."""
+    d = abi.pa_distinct_limit_desc()
+    keep = _distinct_desc(d, input_types, distinct_channels, hash_channel, expected_distinct, output_mem, stream, type_params)
+    d.limit = limit
+    return OperatorFactory(lib().pa_distinct_limit_create, d, keep)
+
+
+def DistinctLimitOperator(input_types, distinct_channels, limit, hash_channel=-1, expected_distinct=0, output_mem=abi.MEM_HOST, stream=None,
+                          type_params=None):
+    return DistinctLimitOperatorFactory(input_types, distinct_channels, limit, hash_channel, expected_distinct, output_mem, stream,
+                                        type_params).createOperator()
 
 
 # ---- driver loop ---------------------------------------------------------------------------------------
