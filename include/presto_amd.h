@@ -450,6 +450,41 @@ typedef struct pa_distinct_limit_desc {  /* DistinctLimitOperatorFactory(sourceT
     void* stream;
 } pa_distinct_limit_desc;
 
+/* RowNumberOperator: `row_number() OVER (PARTITION BY k)` and, with max_rows_per_partition, `... WHERE rn <= m` / "any m rows per key",
+ * planned by LocalExecutionPlanner.visitRowNumber (:900-938) (RowNumberOperator.java: state machine :183-209, getRowsWithRowNumber
+ * :289-299, getSelectedRows :313-342), over GroupByHash.getGroupIds like the two operators above.  The partition of a row is its group
+ * by IS NOT DISTINCT FROM over 0 .. 8 partition channels, under the rules and key types stated for MarkDistinct; PA_LONG_DECIMAL /
+ * PA_ROW partition channels and more than 8 of them are PA_ERR_NOT_SUPPORTED at creation.  Rows are taken in page order: a row gets
+ * count[partition] + 1 and the count goes up by one; counts are int64 and live as long as the operator.  The result does not depend on
+ * how the input is cut into pages and is the same on every run.  No partition channels: one partition, no table.  hash_channel
+ * ($hashvalue) is validated and never read; it is part of the output only if output_channels names it.
+ *   Output page: the input's output_channels in descriptor order, then one BIGINT column without nulls, the row number
+ *     (output_channel_count + 1 channels).
+ *   max_rows_per_partition = -1 (absent): one output page per non-empty input page, of the same length, the input blocks as they are.
+ *     A PA_MEM_DEVICE input page given to a PA_MEM_DEVICE operator comes out with its own blocks and encodings (zero copy); a
+ *     PA_PAGE_RETAINED page is released once its output page has been let go.
+ *   max_rows_per_partition = m >= 0: a row whose partition already stands at m is dropped and does not count; the rows kept come out
+ *     compacted, in input order, as flat copies, numbered count + 1 <= m.  A page that keeps no row produces no page.  Output channels
+ *     of PA_LONG_DECIMAL / PA_ROW are PA_ERR_NOT_SUPPORTED in this mode.
+ *   needs_input = not finishing and no page pending; is_finished = finishing and nothing pending.  Without partition channels and with
+ *     a cap, in addition: needs_input is 0 and is_finished 1 as soon as m rows went out and nothing is pending -- with m = 0, at creation.
+ * Empty input pages are accepted and produce nothing. */
+typedef struct pa_row_number_desc {      /* RowNumberOperatorFactory(sourceTypes, outputChannels, partitionChannels, partitionTypes,
+                                          * maxRowsPerPartition, hashChannel, expectedPositions) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere: VARCHAR(n) bound / PA_DECIMAL_PARAM; NULL = all 0 */
+    int32_t output_channel_count;
+    const int32_t* output_channels;
+    int32_t partition_channel_count;     /* 0 .. 8 */
+    const int32_t* partition_channels;   /* may be NULL when there are none */
+    int32_t hash_channel;                /* or -1 */
+    int32_t expected_positions;          /* first size of the table; 0 = the reference's 10 000 */
+    int64_t max_rows_per_partition;      /* >= 0, or -1 = absent */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_row_number_desc;
+
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
  * factories in one Driver).  Semantically the composition of the three descriptors: the join's probe page is the projection
@@ -675,6 +710,13 @@ int32_t pa_distinct_limit_create(const pa_distinct_limit_desc* desc, pa_operator
  * keys seen so far (nextDistinctId; waits for the pages in flight), *table_capacity = slots of the table (a power of two).  Either
  * pointer may be NULL.  Any other operator: PA_ERR_INVALID_ARGUMENT. */
 int32_t pa_distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* table_capacity);
+
+/* RowNumber (pa_row_number_desc above). */
+int32_t pa_row_number_create(const pa_row_number_desc* desc, pa_operator** out);
+/* GroupByHash.getGroupCount() / getCapacity() of an operator made by pa_row_number_create: *partition_count = the partitions seen so far
+ * (waits for the pages in flight), *table_capacity = slots of the table (a power of two).  Without partition channels: 1 and 0.  Either
+ * pointer may be NULL. */
+int32_t pa_row_number_stats(pa_operator* op, int64_t* partition_count, int64_t* table_capacity);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

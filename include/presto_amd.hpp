@@ -499,6 +499,38 @@ inline int64_t distinctCount(Operator& op)
     return n;
 }
 
+// RowNumberOperatorFactory(sourceTypes, outputChannels, partitionChannels, partitionTypes, maxRowsPerPartition, hashChannel,
+// expectedPositions): the output channels, then the BIGINT row number of each row inside its partition; maxRowsPerPartition = -1: absent
+inline std::unique_ptr<Operator> createRowNumberOperator(const std::vector<int32_t>& inputTypes, const std::vector<int32_t>& outputChannels,
+                                                         const std::vector<int32_t>& partitionChannels, int64_t maxRowsPerPartition = -1,
+                                                         int32_t hashChannel = -1, int32_t expectedPositions = 0, int32_t outputMem = PA_MEM_HOST,
+                                                         const std::vector<int32_t>& typeParams = {})
+{
+    pa_row_number_desc d{};
+    d.input_channel_count = (int32_t)inputTypes.size();
+    d.input_types = inputTypes.data();
+    d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.output_channel_count = (int32_t)outputChannels.size();
+    d.output_channels = outputChannels.data();
+    d.partition_channel_count = (int32_t)partitionChannels.size();
+    d.partition_channels = partitionChannels.data();
+    d.hash_channel = hashChannel;
+    d.expected_positions = expectedPositions;
+    d.max_rows_per_partition = maxRowsPerPartition;
+    d.output_mem = outputMem;
+    pa_operator* h = nullptr;
+    check(pa_row_number_create(&d, &h));
+    return std::make_unique<Operator>(h);
+}
+
+// partitions seen so far of a RowNumber operator
+inline int64_t rowNumberPartitionCount(Operator& op)
+{
+    int64_t n = 0;
+    check(pa_row_number_stats(op.handle(), &n, nullptr));
+    return n;
+}
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

@@ -78,6 +78,12 @@ final class GpuNative
     static native long createDistinctLimit(int[] inputTypes, int[] typeParams, int[] distinctChannels, long limit, int hashChannel, int expectedDistinct, int outputMem);
     /** {distinct keys seen so far, slots of the table} of a MarkDistinct / DistinctLimit operator (GroupByHash.getGroupCount / getCapacity). */
     static native long[] distinctStats(long operator);
+    /** RowNumberOperatorFactory(sourceTypes, outputChannels, partitionChannels, partitionTypes, maxRowsPerPartition, hashChannel, expectedPositions);
+     *  maxRowsPerPartition = -1: absent (GpuRowNumber). */
+    static native long createRowNumber(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] partitionChannels, long maxRowsPerPartition,
+            int hashChannel, int expectedPositions, int outputMem);
+    /** {partitions seen so far, slots of the table} of a RowNumber operator (GroupByHash.getGroupCount / getCapacity). */
+    static native long[] rowNumberStats(long operator);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

@@ -594,6 +594,38 @@ JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_distinctStats(JNIEnv* e
     return out;
 }
 
+/* LocalExecutionPlanner.visitRowNumber: RowNumberOperatorFactory.  maxRowsPerPartition = -1: absent; typeParams as above. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createRowNumber(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,
+        jintArray outputChannels, jintArray partitionChannels, jlong maxRowsPerPartition, jint hashChannel, jint expectedPositions, jint outputMem)
+{
+    jsize n, no, npc, np_ = 0;
+    pa_row_number_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *oc = ints_of(env, outputChannels, &no), *pc = ints_of(env, partitionChannels, &npc);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.output_channel_count = no; d.output_channels = oc; d.partition_channel_count = npc; d.partition_channels = pc;
+    d.hash_channel = hashChannel; d.expected_positions = expectedPositions; d.max_rows_per_partition = maxRowsPerPartition;
+    d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_row_number_create(&d, &op);
+    free(params); free(pc); free(oc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+/* {partitions seen so far, slots of the table} of an operator made by createRowNumber */
+JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_rowNumberStats(JNIEnv* env, jclass c, jlong op)
+{
+    int64_t count = 0, capacity = 0;
+    int32_t rc = pa_row_number_stats((pa_operator*)(intptr_t)op, &count, &capacity);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    jlong v[2] = {(jlong)count, (jlong)capacity};
+    jlongArray out = (*env)->NewLongArray(env, 2);
+    if (out) (*env)->SetLongArrayRegion(env, out, 0, 2, v);
+    return out;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

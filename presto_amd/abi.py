@@ -353,6 +353,23 @@ class pa_distinct_limit_desc(C.Structure):
     ]
 
 
+class pa_row_number_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("output_channel_count", C.c_int32),
+        ("output_channels", C.POINTER(C.c_int32)),
+        ("partition_channel_count", C.c_int32),
+        ("partition_channels", C.POINTER(C.c_int32)),
+        ("hash_channel", C.c_int32),
+        ("expected_positions", C.c_int32),
+        ("max_rows_per_partition", C.c_int64),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

@@ -639,6 +639,25 @@ int32_t pa_distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* tab
     });
 }
 
+// ---- RowNumber ----
+int32_t pa_row_number_create(const pa_row_number_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_row_number(desc);
+        return PA_OK;
+    });
+}
+int32_t pa_row_number_stats(pa_operator* op, int64_t* partition_count, int64_t* table_capacity)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(op != nullptr, PA_ERR_INVALID_ARGUMENT, "operator is null");
+        OpScope scope(op);
+        row_number_stats(op, partition_count, table_capacity);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

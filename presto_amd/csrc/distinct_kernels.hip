@@ -1,4 +1,4 @@
-// distinct_kernels.hip -- the growing key table behind MarkDistinctOperator and DistinctLimitOperator (distinct_kernels.hpp).
+// distinct_kernels.hip -- the growing key table behind MarkDistinctOperator, DistinctLimitOperator and RowNumberOperator (distinct_kernels.hpp).
 //
 // Why no claim / publish protocol is needed inside the insert pass, although workgroups on different XCDs race on the slots:
 //   * a slot word is read and written with agent-scope atomics only (load, compare-and-swap, min);
@@ -66,7 +66,11 @@ __device__ __forceinline__ bool distinct_eq_store(const DistinctKeys& k, i64 i, 
 
 // A workgroup takes 1024 consecutive rows, a lane four of them 256 apart (coalesced key loads).  The four home slots are loaded
 // before the first is looked at: the pass is bound by the latency of dependent slot loads.
-__global__ __launch_bounds__(256) void k_distinct_insert(DistinctKeys keys, DistinctStore store, DistinctTable t, i32* __restrict__ slot_of)
+// kStops (RowNumberOperator): stop_of[i] = the slot row i's probe ended at, whether the row may be first of its key or not -- the slot
+// that holds the key's id once the publish pass has run.  Without it the body is what MarkDistinct / DistinctLimit have always launched.
+template <bool kStops>
+__device__ __forceinline__ void distinct_insert_rows(const DistinctKeys& keys, const DistinctStore& store, const DistinctTable& t, i32* __restrict__ slot_of,
+                                                     i32* __restrict__ stop_of)
 {
     const i64 base = (i64)blockIdx.x * kDistinctRowsPerBlock + threadIdx.x;
     u64 h[4], v[4];
@@ -113,7 +117,18 @@ __global__ __launch_bounds__(256) void k_distinct_insert(DistinctKeys keys, Dist
         }
         // a row that met its key from an earlier page, or at a smaller position of this one, is out: the mark pass need not look
         slot_of[i] = candidate ? (i32)pos : -1;
+        if (kStops) stop_of[i] = (i32)pos;
     }
+}
+
+__global__ __launch_bounds__(256) void k_distinct_insert(DistinctKeys keys, DistinctStore store, DistinctTable t, i32* __restrict__ slot_of)
+{
+    distinct_insert_rows<false>(keys, store, t, slot_of, nullptr);
+}
+__global__ __launch_bounds__(256) void k_distinct_insert_ids(DistinctKeys keys, DistinctStore store, DistinctTable t, i32* __restrict__ slot_of,
+                                                             i32* __restrict__ stop_of)
+{
+    distinct_insert_rows<true>(keys, store, t, slot_of, stop_of);
 }
 
 __device__ __forceinline__ i32 block_sum_256(i32 mine, i32* lds)
@@ -187,6 +202,12 @@ __global__ __launch_bounds__(256) void k_distinct_publish(DistinctPublishArgs a)
     }
 }
 
+// After the publish pass every slot a probe ended at holds tag | id: the group id of every row, as a 64-bit sort key
+__global__ __launch_bounds__(256) void k_distinct_group_ids(DistinctTable t, const i32* __restrict__ stop_of, i32 n, u64* __restrict__ gids)
+{
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) gids[i] = (u64)(u32)slot_load((u64*)t.slots + (u32)stop_of[i]);
+}
+
 __global__ __launch_bounds__(256) void k_distinct_rehash(DistinctStore store, i32 ncols, u32 count, DistinctTable t)
 {
     for (i64 id = (i64)blockIdx.x * 256 + threadIdx.x; id < (i64)count; id += (i64)gridDim.x * 256) {
@@ -219,6 +240,18 @@ void launch_distinct_insert(const DistinctKeys& keys, const DistinctStore& store
 {
     if (keys.n <= 0) return;
     hipLaunchKernelGGL(k_distinct_insert, (int)distinct_blocks(keys.n), 256, 0, s, keys, store, table, slot_of);
+    PA_HIP(hipGetLastError());
+}
+void launch_distinct_insert_ids(const DistinctKeys& keys, const DistinctStore& store, const DistinctTable& table, int32_t* slot_of, int32_t* stop_of, hipStream_t s)
+{
+    if (keys.n <= 0) return;
+    hipLaunchKernelGGL(k_distinct_insert_ids, (int)distinct_blocks(keys.n), 256, 0, s, keys, store, table, slot_of, stop_of);
+    PA_HIP(hipGetLastError());
+}
+void launch_distinct_group_ids(const DistinctTable& table, const int32_t* stop_of, int32_t n, uint64_t* gids, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_distinct_group_ids, distinct_grid(n), 256, 0, s, table, stop_of, n, (u64*)gids);
     PA_HIP(hipGetLastError());
 }
 void launch_distinct_mark(const DistinctTable& table, const int32_t* slot_of, int32_t n, uint8_t* mark, int32_t* block_counts, hipStream_t s)

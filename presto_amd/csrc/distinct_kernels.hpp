@@ -55,6 +55,13 @@ void launch_distinct_canon(const DistinctCanonArgs& a, hipStream_t s);
 // one that stays), -1 when the row met its key from an earlier page or at a smaller position.
 void launch_distinct_insert(const DistinctKeys& keys, const DistinctStore& store, const DistinctTable& table, int32_t* slot_of, hipStream_t s);
 
+// The same pass for an operator that needs the group id of EVERY row (RowNumberOperator): a second instantiation that also writes
+// stop_of[i] = the slot row i's probe ended at (n entries).  Once the publish pass has run, that slot holds tag | id.
+void launch_distinct_insert_ids(const DistinctKeys& keys, const DistinctStore& store, const DistinctTable& table, int32_t* slot_of, int32_t* stop_of,
+                                hipStream_t s);
+// ... and behind the publish pass: gids[i] = id of row i's key (GroupByHash.getGroupIds), widened to the 64-bit keys launch_sort_pairs takes
+void launch_distinct_group_ids(const DistinctTable& table, const int32_t* stop_of, int32_t n, uint64_t* gids, hipStream_t s);
+
 // Pass 3a: mark[i] (round_up(n, 4) bytes) and the marks of each block of kDistinctRowsPerBlock rows (block_counts)
 void launch_distinct_mark(const DistinctTable& table, const int32_t* slot_of, int32_t n, uint8_t* mark, int32_t* block_counts, hipStream_t s);
 inline int64_t distinct_blocks(int64_t n) { return (n + kDistinctRowsPerBlock - 1) / kDistinctRowsPerBlock; }

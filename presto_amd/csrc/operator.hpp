@@ -73,6 +73,9 @@ pa_operator* make_hash_semi_join(const pa_hash_semi_join_desc* desc, pa_channel_
 pa_operator* make_mark_distinct(const pa_mark_distinct_desc* desc);
 pa_operator* make_distinct_limit(const pa_distinct_limit_desc* desc);
 void distinct_stats(pa_operator* op, int64_t* distinct_count, int64_t* table_capacity);
+// RowNumberOperator (op_row_number.cpp); row_number_stats: the partitions seen so far and the table's slots
+pa_operator* make_row_number(const pa_row_number_desc* desc);
+void row_number_stats(pa_operator* op, int64_t* partition_count, int64_t* table_capacity);
 // the consumer of an aggregation's output is a TopN over it: groups that cannot be among its n best rows may be left out (op_fused.cpp, op_fused_output.cpp);
 // false: the operator does not take the hint (it emits everything)
 bool aggregation_set_output_topn(pa_operator* op, int64_t n, const int32_t* sort_channels, const int32_t* sort_orders, int32_t count);

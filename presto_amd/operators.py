@@ -98,6 +98,12 @@ class Operator:
         check(lib().pa_distinct_stats(self._h, C.byref(count), C.byref(capacity)))
         return count.value, capacity.value
 
+    def rowNumberStats(self):
+        """RowNumber only: (partitions seen so far, slots of the table); (1, 0) without partition channels."""
+        count, capacity = C.c_int64(), C.c_int64()
+        check(lib().pa_row_number_stats(self._h, C.byref(count), C.byref(capacity)))
+        return count.value, capacity.value
+
     def setDynamicFilter(self, channel, lookup_source_factory):
         """FilterAndProject only, before the first page: drop the rows whose `channel` value matches no build key of the (built)
         join bridge -- the join's dynamic filter applied upstream of the probe.  True when the filter is active."""
@@ -844,6 +850,42 @@ def DistinctLimitOperator(input_types, distinct_channels, limit, hash_channel=-1
                           type_params=None):
     return DistinctLimitOperatorFactory(input_types, distinct_channels, limit, hash_channel, expected_distinct, output_mem, stream,
                                         type_params).createOperator()
+
+
+# ---- ROW_NUMBER --------------------------------------------------------------------------------------------
+def RowNumberOperatorFactory(input_types, output_channels, partition_channels, max_rows_per_partition=None, hash_channel=-1, expected_positions=0,
+                             output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """RowNumberOperatorFactory(sourceTypes, outputChannels, partitionChannels, partitionTypes, maxRowsPerPartition, hashChannel,
+    expectedPositions) (…/operator/RowNumberOperator.java): the output channels, then the BIGINT row number of each row inside its
+    partition, counted in arrival order over the operator's life; with max_rows_per_partition only the rows numbered up to it."""
+    d = abi.pa_row_number_desc()
+    types = abi.int32_array(input_types)
+    oc = abi.int32_array(output_channels)
+    pc = abi.int32_array(partition_channels)
+    keep = [types, oc, pc]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.output_channel_count = len(output_channels)
+    d.output_channels = C.cast(oc, C.POINTER(C.c_int32))
+    d.partition_channel_count = len(partition_channels)
+    d.partition_channels = C.cast(pc, C.POINTER(C.c_int32))
+    d.hash_channel = hash_channel
+    d.expected_positions = expected_positions
+    d.max_rows_per_partition = -1 if max_rows_per_partition is None else max_rows_per_partition
+    d.output_mem = output_mem
+    d.stream = stream
+    return OperatorFactory(lib().pa_row_number_create, d, keep)
+
+
+def RowNumberOperator(input_types, output_channels, partition_channels, max_rows_per_partition=None, hash_channel=-1, expected_positions=0,
+                      output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    return RowNumberOperatorFactory(input_types, output_channels, partition_channels, max_rows_per_partition, hash_channel, expected_positions,
+                                    output_mem, stream, type_params).createOperator()
 
 
 # ---- driver loop ---------------------------------------------------------------------------------------
