@@ -485,6 +485,62 @@ typedef struct pa_row_number_desc {      /* RowNumberOperatorFactory(sourceTypes
     void* stream;
 } pa_row_number_desc;
 
+/* TopNRankingOperator: `row_number() OVER (PARTITION BY k ORDER BY x) ... WHERE rn <= n` and the same with rank(), planned by
+ * LocalExecutionPlanner.visitTopNRanking as a TopNRankingNode, usually PARTIAL in front of the exchange and FINAL behind it
+ * (TopNRankingOperator.java over GroupedTopNRowNumberBuilder / GroupedTopNRankBuilder).  With n = max_row_count_per_partition:
+ *   Partition of a row: its group under IS NOT DISTINCT FROM over 0 .. 8 partition channels, exactly the rules and key types of
+ *     pa_row_number_desc: PA_LONG_DECIMAL / PA_ROW partition channels and more than 8 of them are PA_ERR_NOT_SUPPORTED at creation (before
+ *     any device work).  No partition channels: one partition, no table.
+ *   Order inside a partition: SimplePageWithPositionComparator over the sort channels -- per channel NULLS FIRST / LAST independent of
+ *     ASC / DESC, DOUBLE / REAL in Double.compare / Float.compare order (NaN largest and equal to itself, -0.0 before +0.0), VARCHAR by
+ *     unsigned bytes with a proper prefix first, BOOLEAN false before true: the order of pa_order_by_desc.  Sort channel types: BIGINT,
+ *     INTEGER, DATE, DOUBLE, REAL, BOOLEAN, VARCHAR (a short DECIMAL is declared BIGINT, as for sorts elsewhere); anything else is
+ *     PA_ERR_NOT_SUPPORTED at creation.
+ *   PA_RANKING_ROW_NUMBER: a partition's rows are numbered 1, 2, ... in that order; rows that compare equal on every sort channel are
+ *     numbered in arrival order (the reference's heap leaves this open; it is what TopN and OrderBy promise here too, and it makes the
+ *     result independent of page cuts and of the run).  Rows numbered <= n are kept.
+ *   PA_RANKING_RANK: rank = 1 + the number of rows of the partition that compare strictly smaller; rows with rank <= n are kept, so a
+ *     partition keeps more than n rows when place n is tied.  Peers are the rows that compare equal under the comparator above (NaN with
+ *     NaN, NULL with NULL); kept peers come out in arrival order.  One deviation: the reference finds peers with IS NOT DISTINCT FROM
+ *     (-0.0 and +0.0 are peers) but orders with Double.compare (they differ), so its own result for a RANK partition holding both zeros
+ *     in a sort channel depends on arrival order; here the comparator decides: they are not peers.
+ *   PA_RANKING_DENSE_RANK: PA_ERR_NOT_SUPPORTED at creation (the reference throws UnsupportedOperationException).
+ *   Output, only after finish: partitions in first-seen order, inside a partition in the order above.  Columns: the input's
+ *     output_channels in descriptor order as flat copies, then -- unless partial -- one BIGINT column without nulls, the row number /
+ *     rank.  partial = 1: the same rows without that column.  An operator that kept nothing produces no page.  How the output is cut
+ *     into pages is not part of the contract.  hash_channel ($hashvalue) is validated and never read.
+ *   needs_input = not finishing; is_finished = finishing and every output page taken; add_input after finish is PA_ERR_ILLEGAL_STATE;
+ *     empty pages are accepted.
+ *   The result is a function of the input row sequence alone: not of page boundaries, of host or device input pages or their encodings,
+ *     of when the operator prunes its state (PRESTO_AMD_TOPN_RANKING_PRUNE_ROWS), or of the run.
+ *   Output channels of PA_LONG_DECIMAL / PA_ROW: PA_ERR_NOT_SUPPORTED.  More rows held at once than INT32_MAX, or the pool limit
+ *     reached: PA_ERR_INSUFFICIENT_RESOURCES.  pa_op_memory_bytes reports table + key store + held rows (+ scratch while allocated);
+ *     the rows held are bounded by what can still be kept, not by the input. */
+typedef enum pa_ranking_type {           /* TopNRankingNode.RankingType */
+    PA_RANKING_ROW_NUMBER = 0, PA_RANKING_RANK = 1, PA_RANKING_DENSE_RANK = 2
+} pa_ranking_type;
+typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingType, sourceTypes, outputChannels, partitionChannels,
+                                          * partitionTypes, sortChannels, sortOrder, maxRowCountPerPartition, partial, hashChannel,
+                                          * expectedPositions) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere; NULL = all 0 */
+    int32_t output_channel_count;
+    const int32_t* output_channels;
+    int32_t partition_channel_count;     /* 0 .. 8 */
+    const int32_t* partition_channels;   /* may be NULL when there are none */
+    int32_t sort_channel_count;          /* > 0 */
+    const int32_t* sort_channels;
+    const int32_t* sort_orders;          /* pa_sort_order per sort channel */
+    int32_t ranking_type;                /* pa_ranking_type */
+    int32_t max_row_count_per_partition; /* > 0 */
+    int32_t partial;                     /* 0 / 1 */
+    int32_t hash_channel;                /* or -1 */
+    int32_t expected_positions;          /* first size of the table; 0 = the reference's 10 000 */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_topn_ranking_desc;
+
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
  * factories in one Driver).  Semantically the composition of the three descriptors: the join's probe page is the projection
@@ -717,6 +773,12 @@ int32_t pa_row_number_create(const pa_row_number_desc* desc, pa_operator** out);
  * (waits for the pages in flight), *table_capacity = slots of the table (a power of two).  Without partition channels: 1 and 0.  Either
  * pointer may be NULL. */
 int32_t pa_row_number_stats(pa_operator* op, int64_t* partition_count, int64_t* table_capacity);
+/* TopNRanking (pa_topn_ranking_desc above). */
+int32_t pa_topn_ranking_create(const pa_topn_ranking_desc* desc, pa_operator** out);
+/* Of an operator made by pa_topn_ranking_create: *partitions = the partitions seen so far (1 without partition channels; waits for the
+ * pages in flight), *capacity = slots of the table (0 without), *rows_held = the rows the operator keeps right now, retained by the last
+ * prune + not yet pruned (what getEstimatedSizeInBytes watches).  Any out pointer may be NULL. */
+int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity, int64_t* rows_held);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

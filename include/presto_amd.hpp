@@ -531,6 +531,63 @@ inline int64_t rowNumberPartitionCount(Operator& op)
     return n;
 }
 
+// TopNRankingOperatorFactory(rankingType, sourceTypes, outputChannels, partitionChannels, partitionTypes, sortChannels, sortOrder,
+// maxRowCountPerPartition, partial, hashChannel, expectedPositions): after finish, the rows whose row_number() / rank() inside their
+// partition is at most maxRowCountPerPartition, as the output channels and -- unless partial -- the BIGINT ranking behind them
+struct TopNRankingOperatorFactory {
+    int32_t rankingType = PA_RANKING_ROW_NUMBER;
+    std::vector<int32_t> sourceTypes, outputChannels, partitionChannels, sortChannels, sortOrders;
+    int32_t maxRowCountPerPartition = 1;
+    bool partial = false;
+    int32_t hashChannel = -1, expectedPositions = 0, outputMem = PA_MEM_HOST;
+    std::vector<int32_t> typeParams;
+
+    TopNRankingOperatorFactory(int32_t rankingType, std::vector<int32_t> sourceTypes, std::vector<int32_t> outputChannels, std::vector<int32_t> partitionChannels,
+                               std::vector<int32_t> sortChannels, std::vector<int32_t> sortOrders, int32_t maxRowCountPerPartition, bool partial,
+                               int32_t hashChannel = -1, int32_t expectedPositions = 0, int32_t outputMem = PA_MEM_HOST)
+        : rankingType(rankingType), sourceTypes(std::move(sourceTypes)), outputChannels(std::move(outputChannels)),
+          partitionChannels(std::move(partitionChannels)), sortChannels(std::move(sortChannels)), sortOrders(std::move(sortOrders)),
+          maxRowCountPerPartition(maxRowCountPerPartition), partial(partial), hashChannel(hashChannel), expectedPositions(expectedPositions),
+          outputMem(outputMem)
+    {
+    }
+
+    std::unique_ptr<Operator> createOperator() const
+    {
+        pa_topn_ranking_desc d{};
+        d.input_channel_count = (int32_t)sourceTypes.size();
+        d.input_types = sourceTypes.data();
+        d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        d.output_channel_count = (int32_t)outputChannels.size();
+        d.output_channels = outputChannels.data();
+        d.partition_channel_count = (int32_t)partitionChannels.size();
+        d.partition_channels = partitionChannels.data();
+        d.sort_channel_count = (int32_t)sortChannels.size();
+        d.sort_channels = sortChannels.data();
+        d.sort_orders = sortOrders.data();
+        d.ranking_type = rankingType;
+        d.max_row_count_per_partition = maxRowCountPerPartition;
+        d.partial = partial ? 1 : 0;
+        d.hash_channel = hashChannel;
+        d.expected_positions = expectedPositions;
+        d.output_mem = outputMem;
+        pa_operator* h = nullptr;
+        check(pa_topn_ranking_create(&d, &h));
+        return std::make_unique<Operator>(h);
+    }
+};
+
+// {partitions seen so far, slots of the table, rows held right now} of a TopNRanking operator
+struct TopNRankingStats {
+    int64_t partitions = 0, capacity = 0, rowsHeld = 0;
+};
+inline TopNRankingStats topNRankingStats(Operator& op)
+{
+    TopNRankingStats st;
+    check(pa_topn_ranking_stats(op.handle(), &st.partitions, &st.capacity, &st.rowsHeld));
+    return st;
+}
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

@@ -84,6 +84,12 @@ final class GpuNative
             int hashChannel, int expectedPositions, int outputMem);
     /** {partitions seen so far, slots of the table} of a RowNumber operator (GroupByHash.getGroupCount / getCapacity). */
     static native long[] rowNumberStats(long operator);
+    /** TopNRankingOperatorFactory(rankingType, sourceTypes, outputChannels, partitionChannels, partitionTypes, sortChannels, sortOrder,
+     *  maxRowCountPerPartition, partial, hashChannel, expectedPositions); rankingType 0 = ROW_NUMBER, 1 = RANK (GpuTopNRanking). */
+    static native long createTopNRanking(int rankingType, int[] inputTypes, int[] typeParams, int[] outputChannels, int[] partitionChannels,
+            int[] sortChannels, int[] sortOrders, int maxRowCountPerPartition, boolean partial, int hashChannel, int expectedPositions, int outputMem);
+    /** {partitions seen so far, slots of the table, rows held right now} of a TopNRanking operator (what getEstimatedSizeInBytes watches). */
+    static native long[] topNRankingStats(long operator);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

@@ -626,6 +626,42 @@ JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_rowNumberStats(JNIEnv* 
     return out;
 }
 
+/* LocalExecutionPlanner.visitTopNRanking: TopNRankingOperatorFactory.  rankingType = pa_ranking_type, sortOrders = SortOrder ordinals;
+ * typeParams as above. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createTopNRanking(JNIEnv* env, jclass c, jint rankingType, jintArray inputTypes, jintArray typeParams,
+        jintArray outputChannels, jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders, jint maxRowCountPerPartition, jboolean partial,
+        jint hashChannel, jint expectedPositions, jint outputMem)
+{
+    jsize n, no, npc, nsc, nso, np_ = 0;
+    pa_topn_ranking_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *oc = ints_of(env, outputChannels, &no), *pc = ints_of(env, partitionChannels, &npc);
+    int32_t *sc = ints_of(env, sortChannels, &nsc), *so = ints_of(env, sortOrders, &nso);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.output_channel_count = no; d.output_channels = oc; d.partition_channel_count = npc; d.partition_channels = pc;
+    d.sort_channel_count = nsc == nso ? nsc : 0; d.sort_channels = sc; d.sort_orders = so;
+    d.ranking_type = rankingType; d.max_row_count_per_partition = maxRowCountPerPartition; d.partial = partial ? 1 : 0;
+    d.hash_channel = hashChannel; d.expected_positions = expectedPositions; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_topn_ranking_create(&d, &op);
+    free(params); free(so); free(sc); free(pc); free(oc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+/* {partitions seen so far, slots of the table, rows held right now} of an operator made by createTopNRanking */
+JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_topNRankingStats(JNIEnv* env, jclass c, jlong op)
+{
+    int64_t partitions = 0, capacity = 0, held = 0;
+    int32_t rc = pa_topn_ranking_stats((pa_operator*)(intptr_t)op, &partitions, &capacity, &held);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    jlong v[3] = {(jlong)partitions, (jlong)capacity, (jlong)held};
+    jlongArray out = (*env)->NewLongArray(env, 3);
+    if (out) (*env)->SetLongArrayRegion(env, out, 0, 3, v);
+    return out;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

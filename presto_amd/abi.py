@@ -370,6 +370,31 @@ class pa_row_number_desc(C.Structure):
     ]
 
 
+RANKING_ROW_NUMBER, RANKING_RANK, RANKING_DENSE_RANK = 0, 1, 2   # pa_ranking_type
+
+
+class pa_topn_ranking_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("output_channel_count", C.c_int32),
+        ("output_channels", C.POINTER(C.c_int32)),
+        ("partition_channel_count", C.c_int32),
+        ("partition_channels", C.POINTER(C.c_int32)),
+        ("sort_channel_count", C.c_int32),
+        ("sort_channels", C.POINTER(C.c_int32)),
+        ("sort_orders", C.POINTER(C.c_int32)),
+        ("ranking_type", C.c_int32),
+        ("max_row_count_per_partition", C.c_int32),
+        ("partial", C.c_int32),
+        ("hash_channel", C.c_int32),
+        ("expected_positions", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

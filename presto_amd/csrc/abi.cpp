@@ -658,6 +658,25 @@ int32_t pa_row_number_stats(pa_operator* op, int64_t* partition_count, int64_t* 
     });
 }
 
+// ---- TopNRanking ----
+int32_t pa_topn_ranking_create(const pa_topn_ranking_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_topn_ranking(desc);
+        return PA_OK;
+    });
+}
+int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity, int64_t* rows_held)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(op != nullptr, PA_ERR_INVALID_ARGUMENT, "operator is null");
+        OpScope scope(op);
+        topn_ranking_stats(op, partitions, capacity, rows_held);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

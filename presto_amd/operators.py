@@ -104,6 +104,12 @@ class Operator:
         check(lib().pa_row_number_stats(self._h, C.byref(count), C.byref(capacity)))
         return count.value, capacity.value
 
+    def topNRankingStats(self):
+        """TopNRanking only: (partitions seen so far, slots of the table, rows held right now: retained by the last prune + not yet pruned)."""
+        partitions, capacity, rows_held = C.c_int64(), C.c_int64(), C.c_int64()
+        check(lib().pa_topn_ranking_stats(self._h, C.byref(partitions), C.byref(capacity), C.byref(rows_held)))
+        return partitions.value, capacity.value, rows_held.value
+
     def setDynamicFilter(self, channel, lookup_source_factory):
         """FilterAndProject only, before the first page: drop the rows whose `channel` value matches no build key of the (built)
         join bridge -- the join's dynamic filter applied upstream of the probe.  True when the filter is active."""
@@ -886,6 +892,50 @@ def RowNumberOperator(input_types, output_channels, partition_channels, max_rows
                       output_mem=abi.MEM_HOST, stream=None, type_params=None):
     return RowNumberOperatorFactory(input_types, output_channels, partition_channels, max_rows_per_partition, hash_channel, expected_positions,
                                     output_mem, stream, type_params).createOperator()
+
+
+# ---- TOP-N RANKING -----------------------------------------------------------------------------------------
+def TopNRankingOperatorFactory(input_types, output_channels, partition_channels, sort_channels, sort_orders, n, ranking_type=abi.RANKING_ROW_NUMBER,
+                               partial=False, hash_channel=-1, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """TopNRankingOperatorFactory(rankingType, sourceTypes, outputChannels, partitionChannels, partitionTypes, sortChannels, sortOrder,
+    maxRowCountPerPartition, partial, hashChannel, expectedPositions) (…/operator/TopNRankingOperator.java): after finish, the rows whose
+    row_number() / rank() inside their partition, under the sort channels, is at most n -- partitions in first-seen order, rows in
+    sort order (ties in arrival order) -- as the output channels and, unless partial, the BIGINT ranking behind them."""
+    d = abi.pa_topn_ranking_desc()
+    types = abi.int32_array(input_types)
+    oc = abi.int32_array(output_channels)
+    pc = abi.int32_array(partition_channels)
+    sc = abi.int32_array(sort_channels)
+    so = abi.int32_array(sort_orders)
+    keep = [types, oc, pc, sc, so]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.output_channel_count = len(output_channels)
+    d.output_channels = C.cast(oc, C.POINTER(C.c_int32))
+    d.partition_channel_count = len(partition_channels)
+    d.partition_channels = C.cast(pc, C.POINTER(C.c_int32))
+    d.sort_channel_count = len(sort_channels)
+    d.sort_channels = C.cast(sc, C.POINTER(C.c_int32))
+    d.sort_orders = C.cast(so, C.POINTER(C.c_int32))
+    d.ranking_type = ranking_type
+    d.max_row_count_per_partition = n
+    d.partial = 1 if partial is True else 0 if partial is False else partial
+    d.hash_channel = hash_channel
+    d.expected_positions = expected_positions
+    d.output_mem = output_mem
+    d.stream = stream
+    return OperatorFactory(lib().pa_topn_ranking_create, d, keep)
+
+
+def TopNRankingOperator(input_types, output_channels, partition_channels, sort_channels, sort_orders, n, ranking_type=abi.RANKING_ROW_NUMBER,
+                        partial=False, hash_channel=-1, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    return TopNRankingOperatorFactory(input_types, output_channels, partition_channels, sort_channels, sort_orders, n, ranking_type, partial,
+                                      hash_channel, expected_positions, output_mem, stream, type_params).createOperator()
 
 
 # ---- driver loop ---------------------------------------------------------------------------------------
