@@ -32,24 +32,28 @@ std::string row_param_names(const RowInputs& s, const std::vector<ChannelLayout>
     return p.str();
 }
 
-// Kernel prologue: wave-uniform facts about the page used by the speculative VARCHAR(1) path.
+// Kernel prologue: wave-uniform facts about the page used by the speculative VARCHAR(1) path.  U<c> -- the page's (range's) n strings
+// hold n bytes in all -- lets a quad whose key bytes are ASCII do without its offsets: VARCHAR(1) allows one code point per string, an
+// ASCII byte is a whole code point, so n such bytes over n strings leave one byte each ("VARCHAR(1) keys without offsets").
 void emit_prologue(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, const ColumnNames& nm)
 {
     for (int c = 0; c < s.n_in; c++) {
         if (!s.used[c] || layout[c].type != PA_VARCHAR || s.short_bound[c] != 1) continue;
         o << "    const i32 P" << c << " = " << nm.n() << " > 0 ? " << nm.o(c) << "[0] : 0;\n";
         o << "    const i64 PB" << c << " = " << nm.n() << " > 0 ? (i64)" << nm.o(c) << "[" << nm.n() << "] - P" << c << " : 0;\n";
+        o << "    const bool U" << c << " = PB" << c << " == (i64)" << nm.n() << ";\n";
     }
 }
 
 // vector loads of row quad q and the 4 argument lists.  All independent loads are issued first (one HBM
 // round trip per step); work that depends on loaded offsets follows.  VARCHAR(1) keys read their 4 bytes
 // speculatively at the position they have when every earlier string of the page is one byte long, and
-// fall back to the offset-dependent path otherwise.
+// fall back to the offset-dependent path otherwise.  Under U<c> (emit_prologue) the quad's offsets are those positions unless one of
+// its bytes is not ASCII: they are computed, not loaded -- after the independent loads, since the choice waits for the key bytes.
 void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, std::string args[4], const ColumnNames& nm)
 {
     static const char* xyzw[4] = {"x", "y", "z", "w"};
-    std::ostringstream post;
+    std::ostringstream mid, post;
     for (int c = 0; c < s.n_in; c++) {
         if (!s.used[c]) continue;
         const std::string C = std::to_string(c), V = nm.v(c), O = nm.o(c), NL = nm.nl(c);
@@ -85,7 +89,15 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
                 for (int r = 0; r < 4; r++) args[r] += ", ((A" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
                 break;
             case PA_VARCHAR: {
-                o << "        pa_i32x4 O" << C << " = ((const pa_i32x4*)" << O << ")[q]; i32 E" << C << " = " << O << "[4 * q + 4];\n";
+                const std::string load_offsets = "O" + C + " = ((const pa_i32x4*)" + O + ")[q]; E" + C + " = " + O + "[4 * q + 4];";
+                if (s.short_bound[c] == 1) {
+                    mid << "        pa_i32x4 O" << C << "; i32 E" << C << ";\n        if (U" << C << " && (K" << C << " & 0x80808080u) == 0u) {\n"
+                        << "            const i32 b = P" << C << " + (i32)(4 * q);\n            O" << C << ".x = b; O" << C << ".y = b + 1; O" << C
+                        << ".z = b + 2; O" << C << ".w = b + 3; E" << C << " = b + 4;\n        } else {\n            " << load_offsets << "\n        }\n";
+                }
+                else {
+                    o << "        pa_i32x4 O" << C << " = ((const pa_i32x4*)" << O << ")[q]; i32 E" << C << " = " << O << "[4 * q + 4];\n";
+                }
                 std::string lo[4], len[4];
                 for (int r = 0; r < 4; r++) {
                     lo[r] = "O" + C + "." + xyzw[r];
@@ -126,7 +138,7 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
             for (int r = 0; r < 4; r++) args[r] += ", ((N" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
         }
     }
-    o << post.str();
+    o << mid.str() << post.str();
 }
 
 std::string VectorVar::load(const std::string& q) const
