@@ -106,6 +106,19 @@ struct OutColumn {
     bool host_ready = false;
 };
 
+// `o` as a zero-copy view of a staged (or held) column
+inline void view_column(OutColumn& o, const DevColumn& src)
+{
+    o.type = src.type;
+    o.varwidth = src.varwidth;
+    o.has_nulls = src.nulls != nullptr;
+    o.view_values = src.values;
+    o.view_offsets = src.offsets;
+    o.view_nulls = src.nulls;
+    o.is_view = true;
+    o.host_ready = false;
+}
+
 // Fills `out` (whose `columns` array has room for cols.size() entries) from device columns; for
 // PA_MEM_HOST copies the first `n` positions to pinned memory and synchronises the stream.
 void publish_output(std::vector<OutColumn>& cols, int32_t n, int32_t mem, hipStream_t stream, pa_page* out,

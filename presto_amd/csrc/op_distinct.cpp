@@ -12,11 +12,9 @@
 // MarkDistinct: output page = input page + that BOOLEAN column (Page.appendColumn).  DistinctLimit: the marked rows' distinct channels
 // (and the hash channel), the first `limit` of them in arrival order.
 //
-// DistinctHash (distinct_hash.hpp) is the table both share: per page canonicalise -> insert -> mark -> scan -> publish.
-#include <deque>
-
-#include "distinct_hash.hpp"
-#include "operator.hpp"
+// DistinctHash (distinct_hash.hpp) is the table both share: per page canonicalise -> insert -> mark -> scan -> publish.  The descriptor
+// checks, and MarkDistinct's output page with the retained input page behind it (PassThroughOutput), are keyed_operator.hpp's.
+#include "keyed_operator.hpp"
 
 namespace pa {
 namespace {
@@ -27,30 +25,13 @@ void check_distinct_desc(int32_t channels, const int32_t* types, int32_t distinc
                          int32_t expected, int32_t output_mem)
 {
     PA_REQUIRE(types != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
-    PA_REQUIRE(channels > 0 && channels <= 64, PA_ERR_NOT_SUPPORTED, "1..64 input channels");
+    check_input_channels(channels);
     PA_REQUIRE(distinct_count > 0 && distinct_channels != nullptr, PA_ERR_INVALID_ARGUMENT, "no distinct channels");
     PA_REQUIRE(distinct_count <= kMaxJoinChannels, PA_ERR_NOT_SUPPORTED, "more distinct channels than the device path takes");
-    for (int32_t i = 0; i < distinct_count; i++) {
-        const int32_t c = distinct_channels[i];
-        PA_REQUIRE(c >= 0 && c < channels, PA_ERR_INVALID_ARGUMENT, "distinct channel out of range");
-        switch (types[c]) {
-            case PA_BIGINT:
-            case PA_INTEGER:
-            case PA_DATE:
-            case PA_DOUBLE:
-            case PA_REAL:
-            case PA_BOOLEAN:
-            case PA_VARCHAR:
-            case PA_DECIMAL: break;
-            case PA_LONG_DECIMAL:
-            case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, "distinct key type not supported on the device");
-            default: throw Error(PA_ERR_INVALID_ARGUMENT, "unknown distinct key type");
-        }
-    }
-    PA_REQUIRE(hash_channel >= -1 && hash_channel < channels, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
-    PA_REQUIRE(hash_channel < 0 || types[hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
+    check_key_channels(distinct_channels, distinct_count, channels, types, "distinct");
+    check_hash_channel(hash_channel, channels, types);
     PA_REQUIRE(expected >= 0, PA_ERR_INVALID_ARGUMENT, "expected_distinct is negative");
-    PA_REQUIRE(output_mem == PA_MEM_HOST || output_mem == PA_MEM_DEVICE, PA_ERR_INVALID_ARGUMENT, "unknown output_mem");
+    check_output_mem(output_mem);
 }
 void* checked_stream(const pa_mark_distinct_desc* d)
 {
@@ -78,9 +59,7 @@ public:
         distinct_channels_.assign(d->distinct_channels, d->distinct_channels + d->distinct_channel_count);
         hash_channel_ = d->hash_channel;
         output_mem_ = d->output_mem;
-        std::vector<int32_t> key_types;
-        for (int32_t c : distinct_channels_) key_types.push_back(types_[c]);
-        hash_.reset(new DistinctHash(key_types, d->expected_distinct, stream_.get()));
+        hash_ = make_distinct_hash(types_, distinct_channels_, d->expected_distinct, stream_.get());
     }
     ~DistinctBase() override { (void)hipStreamSynchronize(stream_.get()); }
     hipStream_t private_stream() override { return stream_.owned() ? stream_.get() : nullptr; }
@@ -94,9 +73,7 @@ public:
 protected:
     const char* add_keys(const DevPage& in, int32_t n, uint8_t* mark, int32_t* out_positions, int64_t limit)
     {
-        const DevColumn* cols[kMaxJoinChannels];
-        for (size_t i = 0; i < distinct_channels_.size(); i++) cols[i] = &in.cols[distinct_channels_[i]];
-        return hash_->add_page(cols, n, mark, out_positions, limit, timer, stream_.get());
+        return hash_->add_page(KeyColumns(in, distinct_channels_).cols, n, mark, out_positions, limit, timer, stream_.get());
     }
     Stream stream_;
     PageStager stager_;
@@ -109,42 +86,34 @@ class MarkDistinctOperator : public DistinctBase {
 public:
     explicit MarkDistinctOperator(const pa_mark_distinct_desc* d) : DistinctBase(d)
     {
-        key_only_.assign(types_.size(), false);
-        for (int32_t c : distinct_channels_) key_only_[c] = true;
+        pass_.init(types_.size(), all_channels(types_.size()), distinct_channels_, output_mem_);
     }
     ~MarkDistinctOperator() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     // the output page may be the input page's own blocks: a retained input page is let go once its output page is
     bool takes_retained() override { return true; }
 
     bool needs_input() override
     {
-        if (!pending_) release_held();
+        if (!pending_) pass_.release(stream_.get());
         return !finishing_ && !pending_;
     }
 
     void add_input(const pa_page* page) override
     {
-        release_held();
-        if (page != nullptr && (page->flags & PA_PAGE_RETAINED) != 0 && page->release != nullptr) held_ = {page->release, page->release_ctx};
+        pass_.release(stream_.get());
+        pass_.hold(page);
         PA_REQUIRE(!finishing_ && !pending_, PA_ERR_ILLEGAL_STATE, "Operator does not need input");
         PA_REQUIRE(page != nullptr && page->channel_count == (int32_t)types_.size(), PA_ERR_INVALID_ARGUMENT, "page does not match the input types");
         const int32_t n = page->position_count;
         if (n <= 0) return;
-        hipStream_t s = stream_.get();
-        zero_copy_ = page->mem == PA_MEM_DEVICE && output_mem_ == PA_MEM_DEVICE;
-        in_ = stager_.stage(page, zero_copy_ ? &key_only_ : nullptr, s);
-        if (zero_copy_) {
-            // Page.appendColumn: the input blocks as they are (their encodings included), the mark behind them
-            dict_copies_.clear();
-            storage_.resize(types_.size() + 1);
-            for (size_t c = 0; c < types_.size(); c++) storage_[c] = copy_column(page->columns[c]);
-        }
+        // Page.appendColumn: the input blocks as they are where they can stay (their encodings included), the mark behind them
+        const DevPage& in = pass_.stage(stager_, page, true, stream_.get());
         uint8_t* mark = static_cast<uint8_t*>(mark_.ensure(((size_t)n + 3) & ~(size_t)3));
-        timer.set_name(add_keys(in_, n, mark, nullptr, 0));
+        timer.set_name(add_keys(in, n, mark, nullptr, 0));
         n_ = n;
         pending_ = true;
     }
@@ -152,50 +121,11 @@ public:
     bool get_output(pa_page* out) override
     {
         if (!pending_) {
-            release_held();
+            pass_.release(stream_.get());
             return false;
         }
         pending_ = false;
-        const size_t nc = types_.size();
-        if (zero_copy_) {
-            pa_column& m = storage_[nc];
-            memset(&m, 0, sizeof m);
-            m.type = PA_BOOLEAN;
-            m.encoding = PA_FLAT;
-            m.values = mark_.ptr();
-            out->position_count = n_;
-            out->channel_count = (int32_t)nc + 1;
-            out->columns = storage_.data();
-            out->mem = PA_MEM_DEVICE;
-            out->flags = 0;
-            out->release = nullptr;
-            out->release_ctx = nullptr;
-            return true;
-        }
-        out_cols_.resize(nc + 1);
-        for (size_t c = 0; c <= nc; c++) {
-            OutColumn& o = out_cols_[c];
-            o.is_view = true;
-            o.host_ready = false;
-            if (c < nc) {
-                const DevColumn& src = in_.cols[c];
-                o.type = src.type;
-                o.varwidth = src.varwidth;
-                o.has_nulls = src.nulls != nullptr;
-                o.view_values = src.values;
-                o.view_offsets = src.offsets;
-                o.view_nulls = src.nulls;
-            }
-            else {
-                o.type = PA_BOOLEAN;
-                o.varwidth = false;
-                o.has_nulls = false;
-                o.view_values = mark_.ptr();
-                o.view_offsets = nullptr;
-                o.view_nulls = nullptr;
-            }
-        }
-        publish_output(out_cols_, n_, output_mem_, stream_.get(), out, storage_);
+        pass_.publish(n_, PA_BOOLEAN, mark_.ptr(), nullptr, stream_.get(), out);
         return true;
     }
 
@@ -204,47 +134,15 @@ public:
     void close() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     int64_t memory_bytes() override { return hash_->memory_bytes() + (int64_t)(stager_.bytes() + mark_.capacity()); }
 
 private:
-    // a block of the input page, its dictionary (DICTIONARY / RLE / ROW_FIELDS) copied: the caller's pa_column structs are its own
-    // again when add_input returns
-    pa_column copy_column(const pa_column& c)
-    {
-        pa_column o = c;
-        if (c.dictionary != nullptr && (c.encoding == PA_DICTIONARY || c.encoding == PA_RLE || c.encoding == PA_ROW_FIELDS)) {
-            const int32_t k = c.encoding == PA_ROW_FIELDS ? c.dictionary_size : 1;
-            dict_copies_.emplace_back(std::max(k, 1));
-            std::vector<pa_column>& held = dict_copies_.back();
-            for (int32_t i = 0; i < k; i++) held[i] = copy_column(c.dictionary[i]);
-            o.dictionary = held.data();
-        }
-        return o;
-    }
-    void release_held()
-    {
-        if (held_.fn == nullptr) return;
-        (void)hipStreamSynchronize(stream_.get());
-        Release r = held_;
-        held_ = {nullptr, nullptr};
-        r.fn(r.ctx);
-    }
-    struct Release {
-        void (*fn)(void*);
-        void* ctx;
-    };
-
-    std::vector<bool> key_only_;
+    PassThroughOutput pass_;
     int32_t n_ = 0;
-    DevPage in_;
     DevBuf mark_;
-    std::vector<OutColumn> out_cols_;
-    std::vector<pa_column> storage_;
-    std::deque<std::vector<pa_column>> dict_copies_;
-    Release held_{nullptr, nullptr};
-    bool zero_copy_ = false, pending_ = false, finishing_ = false;
+    bool pending_ = false, finishing_ = false;
 };
 
 class DistinctLimitOperator : public DistinctBase {

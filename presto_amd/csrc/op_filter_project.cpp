@@ -626,12 +626,9 @@ public:
             const bool identity = e.is_input_ref() && e.node(e.root).channel < spec_.n_in;  // (not a build column of the probe stage)
             if (identity && count == n) {
                 // positionsRange(0, n): InputPageProjection returns block.getRegion -> zero copy
-                const DevColumn& src = in_.cols[e.node(e.root).channel];
-                oc.is_view = true;
-                oc.view_values = src.values;
-                oc.view_offsets = src.offsets;
-                oc.view_nulls = src.nulls;
-                oc.has_nulls = src.nulls != nullptr;
+                view_column(oc, in_.cols[e.node(e.root).channel]);
+                oc.type = e.root_type();   // (the block goes out under the type the projection declares)
+                oc.varwidth = oc.type == PA_VARCHAR;
                 continue;
             }
             if (oc.varwidth) {

@@ -13,12 +13,9 @@
 //
 // Per page with partition channels: DistinctHash::add_page with group ids (canon -> insert -> mark -> scan -> publish -> ids), a stable
 // sort of (id, position) over the bits the distinct count needs, the rank and update passes of row_number_kernels.hpp; with a cap the
-// keep marks -> counts -> scan -> positions -> Block.copyPositions of every output channel and of the row numbers.
-#include <deque>
-
-#include "distinct_hash.hpp"
-#include "operator.hpp"
-#include "row_number_kernels.hpp"
+// keep marks -> counts -> scan -> positions (KeepCompactor) -> Block.copyPositions of every output channel and of the row numbers.
+// Without a cap the output page, with the retained input page behind it, is PassThroughOutput's (both in keyed_operator.hpp).
+#include "keyed_operator.hpp"
 #include "sort_kernels.hpp"
 
 namespace pa {
@@ -30,13 +27,13 @@ void* checked_stream(const pa_row_number_desc* d)
     PA_REQUIRE(d != nullptr && d->input_types != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
     const int32_t channels = d->input_channel_count;
     const int32_t* types = d->input_types;
-    PA_REQUIRE(channels > 0 && channels <= 64, PA_ERR_NOT_SUPPORTED, "1..64 input channels");
+    check_input_channels(channels);
     PA_REQUIRE(d->max_rows_per_partition >= -1, PA_ERR_INVALID_ARGUMENT, "max_rows_per_partition is negative (-1 = absent)");
     PA_REQUIRE(d->output_channel_count >= 0 && (d->output_channel_count == 0 || d->output_channels != nullptr), PA_ERR_INVALID_ARGUMENT, "no output channels");
     PA_REQUIRE(d->output_channel_count <= 64, PA_ERR_NOT_SUPPORTED, "more output channels than the device path takes");
     for (int32_t i = 0; i < d->output_channel_count; i++) {
         const int32_t c = d->output_channels[i];
-        PA_REQUIRE(c >= 0 && c < channels, PA_ERR_INVALID_ARGUMENT, "output channel out of range");
+        check_channels(&c, 1, channels, "output");
         // under a cap the rows kept are copied out position by position: no such copy for 16-byte values and rows
         PA_REQUIRE(d->max_rows_per_partition < 0 || (types[c] != PA_LONG_DECIMAL && types[c] != PA_ROW), PA_ERR_NOT_SUPPORTED,
                    "long decimal / row output channels under max_rows_per_partition");
@@ -44,35 +41,11 @@ void* checked_stream(const pa_row_number_desc* d)
     PA_REQUIRE(d->partition_channel_count >= 0 && (d->partition_channel_count == 0 || d->partition_channels != nullptr), PA_ERR_INVALID_ARGUMENT,
                "partition channels are null");
     PA_REQUIRE(d->partition_channel_count <= kMaxJoinChannels, PA_ERR_NOT_SUPPORTED, "more partition channels than the device path takes");
-    for (int32_t i = 0; i < d->partition_channel_count; i++) {
-        const int32_t c = d->partition_channels[i];
-        PA_REQUIRE(c >= 0 && c < channels, PA_ERR_INVALID_ARGUMENT, "partition channel out of range");
-        switch (types[c]) {
-            case PA_BIGINT:
-            case PA_INTEGER:
-            case PA_DATE:
-            case PA_DOUBLE:
-            case PA_REAL:
-            case PA_BOOLEAN:
-            case PA_VARCHAR:
-            case PA_DECIMAL: break;
-            case PA_LONG_DECIMAL:
-            case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, "partition key type not supported on the device");
-            default: throw Error(PA_ERR_INVALID_ARGUMENT, "unknown partition key type");
-        }
-    }
-    PA_REQUIRE(d->hash_channel >= -1 && d->hash_channel < channels, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
-    PA_REQUIRE(d->hash_channel < 0 || types[d->hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
+    check_key_channels(d->partition_channels, d->partition_channel_count, channels, types, "partition");
+    check_hash_channel(d->hash_channel, channels, types);
     PA_REQUIRE(d->expected_positions >= 0, PA_ERR_INVALID_ARGUMENT, "expected_positions is negative");
-    PA_REQUIRE(d->output_mem == PA_MEM_HOST || d->output_mem == PA_MEM_DEVICE, PA_ERR_INVALID_ARGUMENT, "unknown output_mem");
+    check_output_mem(d->output_mem);
     return d->stream;
-}
-
-int bits_for(int64_t count)
-{
-    int b = 1;
-    while (((int64_t)1 << b) < count) b++;
-    return b;
 }
 
 class RowNumberOperator : public pa_operator {
@@ -83,20 +56,13 @@ public:
         output_channels_.assign(d->output_channels, d->output_channels + d->output_channel_count);
         partition_channels_.assign(d->partition_channels, d->partition_channels + d->partition_channel_count);
         output_mem_ = d->output_mem;
-        key_only_.assign(types_.size(), false);
-        needed_.assign(types_.size(), false);
-        for (int32_t c : partition_channels_) key_only_[c] = needed_[c] = true;
-        for (int32_t c : output_channels_) needed_[c] = true;
-        if (!partition_channels_.empty()) {
-            std::vector<int32_t> key_types;
-            for (int32_t c : partition_channels_) key_types.push_back(types_[c]);
-            hash_.reset(new DistinctHash(key_types, d->expected_positions, stream_.get()));
-        }
+        pass_.init(types_.size(), output_channels_, partition_channels_, output_mem_);
+        hash_ = make_distinct_hash(types_, partition_channels_, d->expected_positions, stream_.get());
     }
     ~RowNumberOperator() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     hipStream_t private_stream() override { return stream_.owned() ? stream_.get() : nullptr; }
     hipStream_t main_stream() override { return stream_.get(); }
@@ -112,7 +78,7 @@ public:
     // RowNumberOperator.java:183-209; the single partition under a cap is done once the cap is reached
     bool needs_input() override
     {
-        if (!pending_) release_held();
+        if (!pending_) pass_.release(stream_.get());
         return !finishing_ && !pending_ && !single_full();
     }
     bool is_finished() override { return !pending_ && (finishing_ || single_full()); }
@@ -120,21 +86,16 @@ public:
 
     void add_input(const pa_page* page) override
     {
-        release_held();
-        if (page != nullptr && (page->flags & PA_PAGE_RETAINED) != 0 && page->release != nullptr) held_ = {page->release, page->release_ctx};
+        pass_.release(stream_.get());
+        pass_.hold(page);
         PA_REQUIRE(!finishing_ && !pending_ && !single_full(), PA_ERR_ILLEGAL_STATE, "Operator does not need input");
         PA_REQUIRE(page != nullptr && page->channel_count == (int32_t)types_.size(), PA_ERR_INVALID_ARGUMENT, "page does not match the input types");
         const int32_t n = page->position_count;
         if (n <= 0) return;
         hipStream_t s = stream_.get();
-        zero_copy_ = cap_ < 0 && page->mem == PA_MEM_DEVICE && output_mem_ == PA_MEM_DEVICE;
-        in_ = stager_.stage(page, zero_copy_ ? &key_only_ : &needed_, s);
-        if (zero_copy_) {
-            // getRowsWithRowNumber: the input blocks as they are (their encodings included), the row numbers behind them
-            dict_copies_.clear();
-            storage_.resize(output_channels_.size() + 1);
-            for (size_t c = 0; c < output_channels_.size(); c++) storage_[c] = copy_column(page->columns[output_channels_[c]]);
-        }
+        // getRowsWithRowNumber: the input blocks as they are where they can stay (their encodings included), the row numbers behind them;
+        // under a cap the rows kept are copied out
+        const DevPage& in = pass_.stage(stager_, page, cap_ < 0, s);
         int64_t* rn = static_cast<int64_t*>(rn_.ensure((size_t)n * 8));
         int32_t kept = n;
         const int32_t* positions = nullptr;
@@ -143,7 +104,7 @@ public:
             if (cap_ >= 0) {
                 kept = (int32_t)std::min<int64_t>(n, cap_ - single_count_);
                 if (kept < n) {   // a prefix of the page (kept > 0: the operator needed input)
-                    int32_t* p = static_cast<int32_t*>(positions_.ensure((size_t)kept * 4));
+                    int32_t* p = static_cast<int32_t*>(kept_rows_.positions.ensure((size_t)kept * 4));
                     launch_row_number_positions_iota(kept, p, s);
                     positions = p;
                 }
@@ -151,20 +112,20 @@ public:
             single_count_ += kept;
         }
         else {
-            number_partitioned(n, rn, s);
-            if (cap_ >= 0) positions = keep_positions(n, &kept, s);
+            number_partitioned(in, n, rn, s);
+            if (cap_ >= 0) positions = kept_rows_.positions_of(keep_.as<uint8_t>(), n, &kept, "row number", s);
         }
         if (kept == 0) return;   // a page that keeps no row produces no page
         if (cap_ >= 0) {
             // getSelectedRows: Block.copyPositions of every output channel (a page kept whole is copied too: the blocks are the
             // operator's own either way), then the row numbers
             if (positions == nullptr) {
-                int32_t* p = static_cast<int32_t*>(positions_.ensure((size_t)kept * 4));
+                int32_t* p = static_cast<int32_t*>(kept_rows_.positions.ensure((size_t)kept * 4));
                 launch_row_number_positions_iota(kept, p, s);
                 positions = p;
             }
             out_cols_.resize(output_channels_.size() + 1);
-            for (size_t c = 0; c < output_channels_.size(); c++) gather_.copy_positions(in_.cols[output_channels_[c]], positions, kept, out_cols_[c], s);
+            for (size_t c = 0; c < output_channels_.size(); c++) gather_.copy_positions(in.cols[output_channels_[c]], positions, kept, out_cols_[c], s);
             OutColumn& o = out_cols_.back();
             o.type = PA_BIGINT;
             o.varwidth = o.has_nulls = o.is_view = o.host_ready = false;
@@ -180,65 +141,24 @@ public:
     bool get_output(pa_page* out) override
     {
         if (!pending_) {
-            release_held();
+            pass_.release(stream_.get());
             return false;
         }
         pending_ = false;
-        const size_t nc = output_channels_.size();
-        if (zero_copy_) {
-            pa_column& m = storage_[nc];
-            memset(&m, 0, sizeof m);
-            m.type = PA_BIGINT;
-            m.encoding = PA_FLAT;
-            m.values = rn_.ptr();
-            out->position_count = n_;
-            out->channel_count = (int32_t)nc + 1;
-            out->columns = storage_.data();
-            out->mem = PA_MEM_DEVICE;
-            out->flags = 0;
-            out->release = nullptr;
-            out->release_ctx = nullptr;
-            return true;
-        }
-        if (cap_ < 0) {
-            out_cols_.resize(nc + 1);
-            for (size_t c = 0; c <= nc; c++) {
-                OutColumn& o = out_cols_[c];
-                o.is_view = true;
-                o.host_ready = false;
-                if (c < nc) {
-                    const DevColumn& src = in_.cols[output_channels_[c]];
-                    o.type = src.type;
-                    o.varwidth = src.varwidth;
-                    o.has_nulls = src.nulls != nullptr;
-                    o.view_values = src.values;
-                    o.view_offsets = src.offsets;
-                    o.view_nulls = src.nulls;
-                }
-                else {
-                    o.type = PA_BIGINT;
-                    o.varwidth = false;
-                    o.has_nulls = false;
-                    o.view_values = rn_.ptr();
-                    o.view_offsets = nullptr;
-                    o.view_nulls = nullptr;
-                }
-            }
-        }
-        publish_output(out_cols_, n_, output_mem_, stream_.get(), out, storage_);
+        if (cap_ < 0) pass_.publish(n_, PA_BIGINT, rn_.ptr(), nullptr, stream_.get(), out);
+        else publish_output(out_cols_, n_, output_mem_, stream_.get(), out, storage_);
         return true;
     }
 
     void close() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     int64_t memory_bytes() override
     {
         size_t b = stager_.bytes() + rn_.capacity() + counts_.capacity() + gids_.capacity() + sorted_gids_.capacity() + sorted_rows_.capacity() +
-                   rows_scratch_.capacity() + sort_temp_.capacity() + mark_.capacity() + keep_.capacity() + positions_.capacity() + block_counts_.capacity() +
-                   scan_temp_.capacity() + total_.capacity() + gather_.bytes();
+                   rows_scratch_.capacity() + sort_temp_.capacity() + mark_.capacity() + keep_.capacity() + kept_rows_.bytes() + gather_.bytes();
         if (cap_ >= 0)
             for (const OutColumn& o : out_cols_) b += o.values.capacity() + o.offsets.capacity() + o.nulls.capacity();
         return (hash_ ? hash_->memory_bytes() : 0) + (int64_t)b;
@@ -248,17 +168,15 @@ private:
     bool single_full() const { return !hash_ && cap_ >= 0 && single_count_ >= cap_; }
 
     // group ids -> stable sort of (id, position) -> rank -> update
-    void number_partitioned(int32_t n, int64_t* rn, hipStream_t s)
+    void number_partitioned(const DevPage& in, int32_t n, int64_t* rn, hipStream_t s)
     {
-        const DevColumn* cols[kMaxJoinChannels];
-        for (size_t i = 0; i < partition_channels_.size(); i++) cols[i] = &in_.cols[partition_channels_[i]];
         uint8_t* mark = static_cast<uint8_t*>(mark_.ensure(((size_t)n + 3) & ~(size_t)3));
         uint64_t* gids = static_cast<uint64_t*>(gids_.ensure((size_t)n * 8));
-        timer.set_name(hash_->add_page(cols, n, mark, nullptr, 0, timer, s, gids));
+        timer.set_name(hash_->add_page(KeyColumns(in, partition_channels_).cols, n, mark, nullptr, 0, timer, s, gids));
         // the partitions seen so far, exact (the wait the sort's bit range is worth: with 4 partitions it is 2 bits, not the 24 an
         // upper bound of a 2^24-row page would give); every id of the page is below it
         const int64_t partitions = hash_->settle(s);
-        grow_counts(partitions, s);
+        grow_by_group_id(counts_, &counts_n_, partitions, 0, s);   // counts by group id; new entries are zero
         uint64_t* sorted_gids = static_cast<uint64_t*>(sorted_gids_.ensure((size_t)n * 8));
         int32_t* sorted_rows = static_cast<int32_t*>(sorted_rows_.ensure((size_t)n * 4));
         int32_t* rows_scratch = static_cast<int32_t*>(rows_scratch_.ensure((size_t)n * 4));
@@ -280,76 +198,19 @@ private:
         launch_row_number_update(sorted_gids, a.tails, n, cap_, counts_.as<int64_t>(), counts_n_, s);
     }
 
-    // counts by group id grow with the key store; new entries are zero
-    void grow_counts(int64_t partitions, hipStream_t s)
-    {
-        if (partitions <= counts_n_) return;
-        const int64_t want = std::max<int64_t>(std::max<int64_t>(partitions, 2 * counts_n_), 1024);
-        counts_.reserve_keep((size_t)want * 8, (size_t)counts_n_ * 8, s);
-        PA_HIP(hipMemsetAsync(counts_.as<int64_t>() + counts_n_, 0, (size_t)(want - counts_n_) * 8, s));
-        counts_n_ = want;
-    }
-
-    // keep marks -> rows kept per block -> scan -> positions; the page's kept-row count comes back to the host
-    const int32_t* keep_positions(int32_t n, int32_t* kept, hipStream_t s)
-    {
-        const int64_t blocks = row_number_blocks(n);
-        int32_t* block_counts = static_cast<int32_t*>(block_counts_.ensure((size_t)blocks * 4));
-        int32_t* total = static_cast<int32_t*>(total_.ensure(64));
-        launch_row_number_keep_counts(keep_.as<uint8_t>(), n, block_counts, s);
-        launch_exclusive_scan_i32(block_counts, block_counts, blocks, total, scan_temp_.ensure(scan_temp_bytes(blocks)), s);
-        int32_t h_total = 0;
-        read_back(&h_total, total, 4, s);
-        PA_REQUIRE(h_total >= 0 && h_total <= n, PA_ERR_DEVICE, "row number: kept rows out of range");
-        *kept = h_total;
-        if (h_total == 0) return nullptr;
-        int32_t* positions = static_cast<int32_t*>(positions_.ensure((size_t)h_total * 4));
-        launch_row_number_keep_positions(keep_.as<uint8_t>(), n, block_counts, positions, s);
-        return positions;
-    }
-
-    // a block of the input page, its dictionary (DICTIONARY / RLE / ROW_FIELDS) copied: the caller's pa_column structs are its own
-    // again when add_input returns
-    pa_column copy_column(const pa_column& c)
-    {
-        pa_column o = c;
-        if (c.dictionary != nullptr && (c.encoding == PA_DICTIONARY || c.encoding == PA_RLE || c.encoding == PA_ROW_FIELDS)) {
-            const int32_t k = c.encoding == PA_ROW_FIELDS ? c.dictionary_size : 1;
-            dict_copies_.emplace_back(std::max(k, 1));
-            std::vector<pa_column>& held = dict_copies_.back();
-            for (int32_t i = 0; i < k; i++) held[i] = copy_column(c.dictionary[i]);
-            o.dictionary = held.data();
-        }
-        return o;
-    }
-    void release_held()
-    {
-        if (held_.fn == nullptr) return;
-        (void)hipStreamSynchronize(stream_.get());
-        Release r = held_;
-        held_ = {nullptr, nullptr};
-        r.fn(r.ctx);
-    }
-    struct Release {
-        void (*fn)(void*);
-        void* ctx;
-    };
-
     Stream stream_;
     PageStager stager_;
     std::unique_ptr<DistinctHash> hash_;   // null: no partition channels
     std::vector<int32_t> types_, output_channels_, partition_channels_;
-    std::vector<bool> key_only_, needed_;
     int64_t cap_ = -1, single_count_ = 0, counts_n_ = 0;
     int32_t output_mem_ = PA_MEM_HOST, n_ = 0;
-    DevPage in_;
-    DevBuf rn_, counts_, gids_, sorted_gids_, sorted_rows_, rows_scratch_, sort_temp_, mark_, keep_, positions_, block_counts_, scan_temp_, total_;
+    PassThroughOutput pass_;   // without a cap: the output page; with one: the staged page and the retained one
+    DevBuf rn_, counts_, gids_, sorted_gids_, sorted_rows_, rows_scratch_, sort_temp_, mark_, keep_;
+    KeepCompactor kept_rows_;
     PositionGather gather_;
-    std::vector<OutColumn> out_cols_;
+    std::vector<OutColumn> out_cols_;   // under a cap: the rows kept, copied out
     std::vector<pa_column> storage_;
-    std::deque<std::vector<pa_column>> dict_copies_;
-    Release held_{nullptr, nullptr};
-    bool zero_copy_ = false, pending_ = false, finishing_ = false;
+    bool pending_ = false, finishing_ = false;
 };
 
 }  // namespace

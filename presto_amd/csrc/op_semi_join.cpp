@@ -20,11 +20,10 @@
 // (semi_join_kernels.hpp) as a BIGINT for every type but VARCHAR, so NaN / -0.0 / BOOLEAN bytes compare right and the keyed layouts
 // (bitmap, rank index, key slots) serve them all; VARCHAR goes through the generic tagged table.  $hashvalue channels are accepted
 // and not read: the canonical key is hashed (a DOUBLE's $hashvalue need not agree for -0.0 and +0.0), so they change no result.
-// Probe: one mark pass per page (semi_join_kernels.hip), one specialisation per layout.
-#include <deque>
-
+// Probe: one mark pass per page (semi_join_kernels.hip), one specialisation per layout; the output page, with the retained probe page
+// behind it, is keyed_operator.hpp's PassThroughOutput.
 #include "join_source.hpp"
-#include "operator.hpp"
+#include "keyed_operator.hpp"
 #include "semi_join_kernels.hpp"
 #include "static_kernels.hpp"
 
@@ -54,47 +53,22 @@ struct pa_channel_set {
 namespace pa {
 namespace {
 
-int32_t semi_key_type(int32_t t)
-{
-    switch (t) {
-        case PA_BIGINT:
-        case PA_INTEGER:
-        case PA_DATE:
-        case PA_DOUBLE:
-        case PA_REAL:
-        case PA_BOOLEAN:
-        case PA_VARCHAR:
-        case PA_DECIMAL: return t;
-        case PA_LONG_DECIMAL:
-        case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, "semi-join key type not supported on the device");
-        default: throw Error(PA_ERR_INVALID_ARGUMENT, "unknown semi-join key type");
-    }
-}
-
-void check_hash_channel(int32_t hash_channel, int32_t count, const int32_t* types)
-{
-    PA_REQUIRE(hash_channel >= -1 && hash_channel < count, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
-    PA_REQUIRE(hash_channel < 0 || types[hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
-}
-
 // the descriptor checks come before the device: a shape the device path does not take is reported as such everywhere
 void* checked_stream(const pa_set_builder_desc* d)
 {
     PA_REQUIRE(d != nullptr && d->input_types != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
     PA_REQUIRE(d->input_channel_count > 0 && d->input_channel_count <= 32, PA_ERR_NOT_SUPPORTED, "1..32 build channels");
-    PA_REQUIRE(d->set_channel >= 0 && d->set_channel < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "set channel out of range");
-    semi_key_type(d->input_types[d->set_channel]);
+    check_key_channels(&d->set_channel, 1, d->input_channel_count, d->input_types, "semi-join");
     check_hash_channel(d->hash_channel, d->input_channel_count, d->input_types);
     return d->stream;
 }
 void* checked_stream(const pa_hash_semi_join_desc* d)
 {
     PA_REQUIRE(d != nullptr && d->probe_types != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
-    PA_REQUIRE(d->probe_channel_count > 0 && d->probe_channel_count <= 64, PA_ERR_NOT_SUPPORTED, "1..64 probe channels");
-    PA_REQUIRE(d->probe_join_channel >= 0 && d->probe_join_channel < d->probe_channel_count, PA_ERR_INVALID_ARGUMENT, "probe join channel out of range");
-    semi_key_type(d->probe_types[d->probe_join_channel]);
+    check_input_channels(d->probe_channel_count);
+    check_key_channels(&d->probe_join_channel, 1, d->probe_channel_count, d->probe_types, "semi-join");
     check_hash_channel(d->probe_hash_channel, d->probe_channel_count, d->probe_types);
-    PA_REQUIRE(d->output_mem == PA_MEM_HOST || d->output_mem == PA_MEM_DEVICE, PA_ERR_INVALID_ARGUMENT, "unknown output_mem");
+    check_output_mem(d->output_mem);
     return d->stream;
 }
 
@@ -233,16 +207,14 @@ public:
         key_channel_ = d->probe_join_channel;
         key_param_ = types_[key_channel_] == PA_DECIMAL && d->probe_type_params ? d->probe_type_params[key_channel_] : 0;
         check_key_type();
-        output_mem_ = d->output_mem;
-        key_only_.assign(types_.size(), false);
-        key_only_[key_channel_] = true;
+        pass_.init(types_.size(), all_channels(types_.size()), {key_channel_}, d->output_mem);
         flag_ = static_cast<int32_t*>(flag_buf_.ensure(64));
         h_flag_ = static_cast<int32_t*>(h_flag_buf_.ensure(64));
     }
     ~HashSemiJoinOperator() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     hipStream_t private_stream() override { return stream_.owned() ? stream_.get() : nullptr; }
     hipStream_t main_stream() override { return stream_.get(); }
@@ -251,7 +223,7 @@ public:
 
     bool needs_input() override
     {
-        if (!pending_) release_held();
+        if (!pending_) pass_.release(stream_.get());
         if (set_->built.load() && set_->error.load() != 0) throw Error(set_->error.load(), "the set's build failed on device");
         return !finishing_ && !pending_ && set_->built.load();
     }
@@ -259,8 +231,8 @@ public:
 
     void add_input(const pa_page* page) override
     {
-        release_held();
-        if (page != nullptr && (page->flags & PA_PAGE_RETAINED) != 0 && page->release != nullptr) held_ = {page->release, page->release_ctx};
+        pass_.release(stream_.get());
+        pass_.hold(page);
         PA_REQUIRE(set_->built.load(), PA_ERR_ILLEGAL_STATE, "the set is not built yet");
         if (set_->error.load() != 0) throw Error(set_->error.load(), "the set's build failed on device");
         PA_REQUIRE(!finishing_ && !pending_, PA_ERR_ILLEGAL_STATE, "Operator does not need input");
@@ -269,15 +241,8 @@ public:
         const int32_t n = page->position_count;
         if (n <= 0) return;   // (LookupJoinOperator: a zero-row page produces nothing)
         hipStream_t s = stream_.get();
-        zero_copy_ = page->mem == PA_MEM_DEVICE && output_mem_ == PA_MEM_DEVICE;
-        in_ = stager_.stage(page, zero_copy_ ? &key_only_ : nullptr, s);
-        if (zero_copy_) {
-            // Page.appendColumn: the input blocks as they are (their encodings included), the mark behind them
-            dict_copies_.clear();
-            storage_.resize(types_.size() + 1);
-            for (size_t c = 0; c < types_.size(); c++) storage_[c] = copy_column(page->columns[c]);
-        }
-        const DevColumn& key = in_.cols[key_channel_];
+        // Page.appendColumn: the input blocks as they are where they can stay (their encodings included), the mark behind them
+        const DevColumn& key = pass_.stage(stager_, page, true, s).cols[key_channel_];
         PA_REQUIRE(key.type == types_[key_channel_], PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared probe type");
         const ChannelSetImpl& set = *set_;
         SemiProbeArgs a;
@@ -328,7 +293,7 @@ public:
     bool get_output(pa_page* out) override
     {
         if (!pending_) {
-            release_held();
+            pass_.release(stream_.get());
             return false;
         }
         pending_ = false;
@@ -338,47 +303,7 @@ public:
             PA_HIP(hipStreamSynchronize(s));
             null_marks = *h_flag_ != 0;
         }
-        const size_t nc = types_.size();
-        if (zero_copy_) {
-            pa_column& m = storage_[nc];
-            memset(&m, 0, sizeof m);
-            m.type = PA_BOOLEAN;
-            m.encoding = PA_FLAT;
-            m.values = mark_.ptr();
-            m.nulls = null_marks ? mark_null_.as<uint8_t>() : nullptr;
-            out->position_count = n_;
-            out->channel_count = (int32_t)nc + 1;
-            out->columns = storage_.data();
-            out->mem = PA_MEM_DEVICE;
-            out->flags = 0;
-            out->release = nullptr;
-            out->release_ctx = nullptr;
-            return true;
-        }
-        out_cols_.resize(nc + 1);
-        for (size_t c = 0; c <= nc; c++) {
-            OutColumn& o = out_cols_[c];
-            o.is_view = true;
-            o.host_ready = false;
-            if (c < nc) {
-                const DevColumn& src = in_.cols[c];
-                o.type = src.type;
-                o.varwidth = src.varwidth;
-                o.has_nulls = src.nulls != nullptr;
-                o.view_values = src.values;
-                o.view_offsets = src.offsets;
-                o.view_nulls = src.nulls;
-            }
-            else {
-                o.type = PA_BOOLEAN;
-                o.varwidth = false;
-                o.has_nulls = null_marks;
-                o.view_values = mark_.ptr();
-                o.view_offsets = nullptr;
-                o.view_nulls = null_marks ? mark_null_.as<uint8_t>() : nullptr;
-            }
-        }
-        publish_output(out_cols_, n_, output_mem_, s, out, storage_);
+        pass_.publish(n_, PA_BOOLEAN, mark_.ptr(), null_marks ? mark_null_.as<uint8_t>() : nullptr, s, out);
         return true;
     }
 
@@ -387,7 +312,7 @@ public:
     void close() override
     {
         (void)hipStreamSynchronize(stream_.get());
-        release_held();
+        pass_.release(stream_.get());
     }
     int64_t memory_bytes() override { return (int64_t)(stager_.bytes() + mark_.capacity() + mark_null_.capacity() + hash_.capacity()); }
 
@@ -400,45 +325,18 @@ private:
         PA_REQUIRE(t == types_[key_channel_], PA_ERR_INVALID_ARGUMENT, "probe / set key types differ");
         PA_REQUIRE(t != PA_DECIMAL || set_->type_param.load() == key_param_, PA_ERR_INVALID_ARGUMENT, "probe / set DECIMAL precision or scale differ");
     }
-    // a block of the input page, its dictionary (DICTIONARY / RLE / ROW_FIELDS) copied: the caller's pa_column structs are its own
-    // again when add_input returns
-    pa_column copy_column(const pa_column& c)
-    {
-        pa_column o = c;
-        if (c.dictionary != nullptr && (c.encoding == PA_DICTIONARY || c.encoding == PA_RLE || c.encoding == PA_ROW_FIELDS)) {
-            const int32_t k = c.encoding == PA_ROW_FIELDS ? c.dictionary_size : 1;
-            dict_copies_.emplace_back(std::max(k, 1));
-            std::vector<pa_column>& held = dict_copies_.back();
-            for (int32_t i = 0; i < k; i++) held[i] = copy_column(c.dictionary[i]);
-            o.dictionary = held.data();
-        }
-        return o;
-    }
-    void release_held()
-    {
-        if (held_.fn == nullptr) return;
-        (void)hipStreamSynchronize(stream_.get());
-        LookupSourceImpl::Release r = held_;
-        held_ = {nullptr, nullptr};
-        r.fn(r.ctx);
-    }
 
     Stream stream_;
     PageStager stager_;
     std::shared_ptr<ChannelSetImpl> set_;
     std::vector<int32_t> types_;
-    std::vector<bool> key_only_;
-    int32_t key_channel_ = 0, key_param_ = 0, output_mem_ = PA_MEM_HOST, n_ = 0;
-    DevPage in_;
+    PassThroughOutput pass_;
+    int32_t key_channel_ = 0, key_param_ = 0, n_ = 0;
     DevBuf mark_, mark_null_, hash_, flag_buf_;
     PinnedBuf h_flag_buf_;
     int32_t* flag_ = nullptr;
     int32_t* h_flag_ = nullptr;
-    std::vector<OutColumn> out_cols_;
-    std::vector<pa_column> storage_;
-    std::deque<std::vector<pa_column>> dict_copies_;
-    LookupSourceImpl::Release held_{nullptr, nullptr};
-    bool zero_copy_ = false, may_null_ = false, pending_ = false, finishing_ = false;
+    bool may_null_ = false, pending_ = false, finishing_ = false;
 };
 
 }  // namespace

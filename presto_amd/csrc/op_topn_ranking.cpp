@@ -14,8 +14,8 @@
 // State is bounded by what can still matter.  The operator holds rows, column by column, as [rows retained by the last prune | rows
 // appended since]:
 //   per page   group ids (DistinctHash::add_page), the image of the first sort channel (launch_topn_keys), the arrival filter
-//              keep = image <= bound[gid] (topn_ranking_kernels.hpp), keep counts -> scan -> positions, Block.copyPositions of the
-//              survivors behind the held rows;
+//              keep = image <= bound[gid] (topn_ranking_kernels.hpp), keep counts -> scan -> positions (KeepCompactor,
+//              keyed_operator.hpp), Block.copyPositions of the survivors behind the held rows;
 //   prune      when the rows appended since the last prune reach max(threshold, rows retained by it), and at finish: the held rows
 //              sorted by (gid, sort channels) (row_sort.hpp), numbered / ranked, the rows kept gathered into fresh columns, bound[gid]
 //              rewritten for every partition that holds n rows.
@@ -24,9 +24,7 @@
 // dropped under a tighter one.  A prune itself drops only rows that n others strictly precede (ROW_NUMBER: in (order, arrival)).
 #include <cstdlib>
 
-#include "distinct_hash.hpp"
-#include "operator.hpp"
-#include "row_number_kernels.hpp"
+#include "keyed_operator.hpp"
 #include "row_sort.hpp"
 #include "topn_ranking_kernels.hpp"
 
@@ -41,7 +39,7 @@ void* checked_stream(const pa_topn_ranking_desc* d)
     PA_REQUIRE(d != nullptr && d->input_types != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
     const int32_t channels = d->input_channel_count;
     const int32_t* types = d->input_types;
-    PA_REQUIRE(channels > 0 && channels <= 64, PA_ERR_NOT_SUPPORTED, "1..64 input channels");
+    check_input_channels(channels);
     PA_REQUIRE(d->ranking_type == PA_RANKING_ROW_NUMBER || d->ranking_type == PA_RANKING_RANK || d->ranking_type == PA_RANKING_DENSE_RANK,
                PA_ERR_INVALID_ARGUMENT, "unknown ranking_type");
     PA_REQUIRE(d->max_row_count_per_partition > 0, PA_ERR_INVALID_ARGUMENT, "max_row_count_per_partition must be positive");
@@ -50,18 +48,16 @@ void* checked_stream(const pa_topn_ranking_desc* d)
     PA_REQUIRE(d->partition_channel_count >= 0 && (d->partition_channel_count == 0 || d->partition_channels != nullptr), PA_ERR_INVALID_ARGUMENT,
                "partition channels are null");
     PA_REQUIRE(d->sort_channel_count > 0 && d->sort_channels != nullptr && d->sort_orders != nullptr, PA_ERR_INVALID_ARGUMENT, "no sort channels");
-    for (int32_t i = 0; i < d->output_channel_count; i++)
-        PA_REQUIRE(d->output_channels[i] >= 0 && d->output_channels[i] < channels, PA_ERR_INVALID_ARGUMENT, "output channel out of range");
-    for (int32_t i = 0; i < d->partition_channel_count && i < kMaxJoinChannels + 1; i++)
-        PA_REQUIRE(d->partition_channels[i] >= 0 && d->partition_channels[i] < channels, PA_ERR_INVALID_ARGUMENT, "partition channel out of range");
+    check_channels(d->output_channels, d->output_channel_count, channels, "output");
+    // (a channel out of range is reported before a count the device path does not take: of a longer list, the first channels only)
+    check_channels(d->partition_channels, std::min(d->partition_channel_count, kMaxJoinChannels + 1), channels, "partition");
     for (int32_t i = 0; i < d->sort_channel_count; i++) {
-        PA_REQUIRE(d->sort_channels[i] >= 0 && d->sort_channels[i] < channels, PA_ERR_INVALID_ARGUMENT, "sort channel out of range");
+        check_channels(d->sort_channels + i, 1, channels, "sort");
         PA_REQUIRE(d->sort_orders[i] >= 0 && d->sort_orders[i] <= 3, PA_ERR_INVALID_ARGUMENT, "unknown sort order");
     }
-    PA_REQUIRE(d->hash_channel >= -1 && d->hash_channel < channels, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
-    PA_REQUIRE(d->hash_channel < 0 || types[d->hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
+    check_hash_channel(d->hash_channel, channels, types);
     PA_REQUIRE(d->expected_positions >= 0, PA_ERR_INVALID_ARGUMENT, "expected_positions is negative");
-    PA_REQUIRE(d->output_mem == PA_MEM_HOST || d->output_mem == PA_MEM_DEVICE, PA_ERR_INVALID_ARGUMENT, "unknown output_mem");
+    check_output_mem(d->output_mem);
     // what the device path does not take
     PA_REQUIRE(d->ranking_type != PA_RANKING_DENSE_RANK, PA_ERR_NOT_SUPPORTED, "dense_rank (the reference does not take it either)");
     PA_REQUIRE(d->output_channel_count <= 64, PA_ERR_NOT_SUPPORTED, "more output channels than the device path takes");
@@ -72,21 +68,7 @@ void* checked_stream(const pa_topn_ranking_desc* d)
         // the rows kept are copied position by position: no such copy for 16-byte values and rows
         PA_REQUIRE(t != PA_LONG_DECIMAL && t != PA_ROW, PA_ERR_NOT_SUPPORTED, "long decimal / row output channels");
     }
-    for (int32_t i = 0; i < d->partition_channel_count; i++) {
-        switch (types[d->partition_channels[i]]) {
-            case PA_BIGINT:
-            case PA_INTEGER:
-            case PA_DATE:
-            case PA_DOUBLE:
-            case PA_REAL:
-            case PA_BOOLEAN:
-            case PA_VARCHAR:
-            case PA_DECIMAL: break;
-            case PA_LONG_DECIMAL:
-            case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, "partition key type not supported on the device");
-            default: throw Error(PA_ERR_INVALID_ARGUMENT, "unknown partition key type");
-        }
-    }
+    for (int32_t i = 0; i < d->partition_channel_count; i++) check_key_type(types[d->partition_channels[i]], "partition");
     for (int32_t i = 0; i < d->sort_channel_count; i++) {
         switch (types[d->sort_channels[i]]) {
             case PA_BIGINT:
@@ -103,13 +85,6 @@ void* checked_stream(const pa_topn_ranking_desc* d)
         }
     }
     return d->stream;
-}
-
-int bits_for(int64_t count)
-{
-    int b = 1;
-    while (((int64_t)1 << b) < count) b++;
-    return b;
 }
 
 DevColumn view_of(const OutColumn& o)
@@ -151,11 +126,7 @@ public:
             if (v > 0) threshold_ = v;
         }
         hipStream_t s = stream_.get();
-        if (!partition_channels_.empty()) {
-            std::vector<int32_t> key_types;
-            for (int32_t c : partition_channels_) key_types.push_back(types_[c]);
-            hash_.reset(new DistinctHash(key_types, d->expected_positions, s));
-        }
+        hash_ = make_distinct_hash(types_, partition_channels_, d->expected_positions, s);
         grow_bounds(1, s);
         timer.set_name("k_topn_ranking_filter");
     }
@@ -187,10 +158,8 @@ public:
         // group ids in first-seen order; one partition: id 0
         uint64_t* gids = static_cast<uint64_t*>(gids_.ensure((size_t)n * 8));
         if (hash_) {
-            const DevColumn* cols[kMaxJoinChannels];
-            for (size_t i = 0; i < partition_channels_.size(); i++) cols[i] = &in.cols[partition_channels_[i]];
             uint8_t* mark = static_cast<uint8_t*>(mark_.ensure(((size_t)n + 3) & ~(size_t)3));
-            hash_->add_page(cols, n, mark, nullptr, 0, table_timer_, s, gids);
+            hash_->add_page(KeyColumns(in, partition_channels_).cols, n, mark, nullptr, 0, table_timer_, s, gids);
         }
         else PA_HIP(hipMemsetAsync(gids, 0, (size_t)n * 8, s));
         // the first sort channel's image with its NULL placement folded in: image order never contradicts comparator order
@@ -208,7 +177,7 @@ public:
             launch_topn_ranking_filter(gids + at, images + at, bound_.as<uint64_t>(), bound_n_, m, keep, s);
             timer.end(s);
             int32_t kept = 0;
-            const int32_t* positions = keep_positions(keep, m, &kept, s);
+            const int32_t* positions = kept_rows_.positions_of(keep, m, &kept, "topn ranking", s);
             if (kept > 0) {
                 if (rows_ + kept > INT32_MAX) prune(s);
                 PA_REQUIRE(rows_ + kept <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "more rows held than one sort takes");
@@ -231,26 +200,11 @@ public:
         const size_t nc = output_channels_.size();
         out_cols_.clear();
         out_cols_.resize(nc + (partial_ ? 0 : 1));
-        for (size_t c = 0; c < out_cols_.size(); c++) {
-            OutColumn& o = out_cols_[c];
-            o.is_view = true;
-            o.host_ready = false;
-            if (c < nc) {
-                const DevColumn src = view_of(held_[output_channels_[c]]);
-                o.type = src.type;
-                o.varwidth = src.varwidth;
-                o.has_nulls = src.nulls != nullptr;
-                o.view_values = src.values;
-                o.view_offsets = src.offsets;
-                o.view_nulls = src.nulls;
-            }
-            else {
-                o.type = PA_BIGINT;
-                o.varwidth = o.has_nulls = false;
-                o.view_values = ranking_kept_.ptr();
-                o.view_offsets = nullptr;
-                o.view_nulls = nullptr;
-            }
+        for (size_t c = 0; c < nc; c++) view_column(out_cols_[c], view_of(held_[output_channels_[c]]));
+        if (!partial_) {
+            DevColumn ranking;   // BIGINT, flat, no nulls
+            ranking.values = ranking_kept_.ptr();
+            view_column(out_cols_[nc], ranking);
         }
         publish_output(out_cols_, (int32_t)rows_, output_mem_, s, out, storage_);
         return true;
@@ -261,8 +215,7 @@ public:
     // table + key store + held rows, and the scratch of a page / a prune while it is allocated
     int64_t memory_bytes() override
     {
-        size_t b = stager_.bytes() + gids_.capacity() + images_.capacity() + mark_.capacity() + keep_.capacity() + positions_.capacity() + block_counts_.capacity() +
-                   scan_temp_.capacity() + total_.capacity() + gather_.bytes() + held_gids_.capacity() + bound_.capacity() + run_start_.capacity() +
+        size_t b = stager_.bytes() + gids_.capacity() + images_.capacity() + mark_.capacity() + keep_.capacity() + kept_rows_.bytes() + gather_.bytes() + held_gids_.capacity() + bound_.capacity() + run_start_.capacity() +
                    ranking_kept_.capacity() + sorter_.bytes() + varchar_tmp_.values.capacity() + varchar_tmp_.offsets.capacity() + varchar_tmp_.nulls.capacity();
         for (const OutColumn& o : held_) b += o.values.capacity() + o.offsets.capacity() + o.nulls.capacity();
         return (hash_ ? hash_->memory_bytes() : 0) + (int64_t)b;
@@ -285,32 +238,7 @@ private:
     }
 
     // bound[] by group id, ~0 for partitions that do not hold n rows yet
-    void grow_bounds(int64_t partitions, hipStream_t s)
-    {
-        if (partitions <= bound_n_) return;
-        const int64_t want = std::max<int64_t>(std::max<int64_t>(partitions, 2 * bound_n_), 1024);
-        bound_.reserve_keep((size_t)want * 8, (size_t)bound_n_ * 8, s);
-        PA_HIP(hipMemsetAsync(bound_.as<uint64_t>() + bound_n_, 0xff, (size_t)(want - bound_n_) * 8, s));
-        bound_n_ = want;
-    }
-
-    // keep marks -> rows kept per block -> scan -> positions; the count comes back to the host
-    const int32_t* keep_positions(const uint8_t* keep, int64_t n, int32_t* kept, hipStream_t s)
-    {
-        const int64_t blocks = row_number_blocks(n);
-        int32_t* block_counts = static_cast<int32_t*>(block_counts_.ensure((size_t)blocks * 4));
-        int32_t* total = static_cast<int32_t*>(total_.ensure(64));
-        launch_row_number_keep_counts(keep, (int32_t)n, block_counts, s);
-        launch_exclusive_scan_i32(block_counts, block_counts, blocks, total, scan_temp_.ensure(scan_temp_bytes(blocks)), s);
-        int32_t h_total = 0;
-        read_back(&h_total, total, 4, s);
-        PA_REQUIRE(h_total >= 0 && h_total <= n, PA_ERR_DEVICE, "topn ranking: kept rows out of range");
-        *kept = h_total;
-        if (h_total == 0) return nullptr;
-        int32_t* positions = static_cast<int32_t*>(positions_.ensure((size_t)h_total * 4));
-        launch_row_number_keep_positions(keep, (int32_t)n, block_counts, positions, s);
-        return positions;
-    }
+    void grow_bounds(int64_t partitions, hipStream_t s) { grow_by_group_id(bound_, &bound_n_, partitions, 0xff, s); }
 
     // Block.copyPositions of the page's survivors behind the held rows, with their group ids
     void append(const DevPage& in, const uint64_t* gids, const int32_t* positions, int32_t k, hipStream_t s)
@@ -382,7 +310,7 @@ private:
             int32_t* peer_index = static_cast<int32_t*>(peer_index_buf.ensure((size_t)n * 4));
             int32_t* peer_start = static_cast<int32_t*>(peer_start_buf.ensure((size_t)n * 4));
             launch_topn_ranking_heads(sorted_gids, differs, (int32_t)n, run_start, bound_n_, peer_flag, s);
-            launch_exclusive_scan_i32(peer_flag, peer_index, n, static_cast<int32_t*>(total_.ensure(64)), scan_temp_.ensure(scan_temp_bytes(n)), s);
+            launch_exclusive_scan_i32(peer_flag, peer_index, n, static_cast<int32_t*>(kept_rows_.total.ensure(64)), kept_rows_.scan_temp.ensure(scan_temp_bytes(n)), s);
             launch_topn_ranking_peer_starts(peer_flag, peer_index, (int32_t)n, peer_start, s);
             a.peer_flag = peer_flag;
             a.peer_index = peer_index;
@@ -404,7 +332,7 @@ private:
         a.n = (int32_t)n;
         launch_topn_ranking_rank(a, s);
         int32_t kept = 0;
-        const int32_t* sorted_positions = keep_positions(a.keep, n, &kept, s);
+        const int32_t* sorted_positions = kept_rows_.positions_of(a.keep, (int32_t)n, &kept, "topn ranking", s);
         PA_REQUIRE(kept > 0, PA_ERR_DEVICE, "topn ranking: a prune kept nothing");
         int32_t* rowids = static_cast<int32_t*>(rowids_buf.ensure((size_t)kept * 4));
         launch_gather_flat(perm, 4, sorted_positions, kept, rowids, s);
@@ -447,7 +375,8 @@ private:
     int64_t rows_ = 0, retained_ = 0, appended_ = 0;
     DevBuf bound_, run_start_;
     int64_t bound_n_ = 0;
-    DevBuf gids_, images_, mark_, keep_, positions_, block_counts_, scan_temp_, total_, ranking_kept_;
+    DevBuf gids_, images_, mark_, keep_, ranking_kept_;
+    KeepCompactor kept_rows_;   // (its scan scratch also serves the scan of the peer flags in a prune)
     PositionGather gather_;
     OutColumn varchar_tmp_;
     RowSorter sorter_;

@@ -406,6 +406,49 @@ def test_pass_through_channels_are_the_input(gpu):
     op.close()
 
 
+def test_mark_distinct_retained_pages_are_released_exactly_once(gpu):
+    """A PA_PAGE_RETAINED page is released once its output page has been let go -- not before (the zero-copy output page IS the input's
+    blocks: the release callback scribbles over them) -- and exactly once, also when the operator is closed over a pending output."""
+    from tests.test_gpu_row_number import host_page_of, raw_output
+    from tests.test_gpu_small_pages import retained_pages
+    n = 5000
+    keys = np.arange(n, dtype=np.int64) % 97
+    host = Page([Block.bigint(keys), Block.double(np.arange(n, dtype=np.float64))], n)
+    bounds = [0, 700, 701, 2000, n]
+    want = numpy_marks(keys)
+    released = []
+    pages = retained_pages(host, bounds, released)
+    op = MarkDistinctOperator([abi.BIGINT, abi.DOUBLE], [0], output_mem=abi.MEM_DEVICE)
+    for i, p in enumerate(pages):
+        lo, hi = bounds[i], bounds[i + 1]
+        assert op.needsInput()
+        op.addInput(p)
+        assert released == list(range(i))                                # page i is still held
+        out = raw_output(op)
+        assert out is not None and out.mem == abi.MEM_DEVICE and out.position_count == hi - lo and out.channel_count == 3
+        got = host_page_of(op, out)                                      # reads the caller's blocks: they must still be intact
+        assert np.array_equal(got.blocks[0].values[:hi - lo], keys[lo:hi])
+        assert np.array_equal(got.blocks[1].values[:hi - lo], np.arange(lo, hi, dtype=np.float64))
+        assert np.array_equal(got.blocks[2].values[:hi - lo], want[lo:hi])
+        assert released == list(range(i))                                # ... while its output page is out
+        op.needsInput()                                                  # the output page has been let go
+        assert released == list(range(i + 1))
+    op.finish()
+    op.close()
+    assert released == list(range(len(pages)))
+
+    # closed while an output page is still pending: the page goes back once, at close
+    released = []
+    pages = retained_pages(host, bounds, released)
+    op = MarkDistinctOperator([abi.BIGINT, abi.DOUBLE], [0], output_mem=abi.MEM_DEVICE)
+    op.addInput(pages[0])
+    assert not op.needsInput() and released == []
+    op.close()
+    assert released == [0]
+    del op
+    assert released == [0]
+
+
 def test_empty_pages_and_protocol(gpu):
     op = MarkDistinctOperator([abi.BIGINT], [0])
     empty = Page([Block.bigint([])], 0)

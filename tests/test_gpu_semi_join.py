@@ -359,6 +359,54 @@ def test_pass_through_channels_are_the_input(gpu):
     j.close()
 
 
+def test_semi_join_retained_pages_are_released_exactly_once(gpu):
+    """A PA_PAGE_RETAINED probe page is released once its output page has been let go -- not before (the zero-copy output page IS the
+    input's blocks: the release callback scribbles over them) -- and exactly once, also when the operator is closed over a pending
+    output.  The set holds a NULL, so every miss is a NULL mark: the mark column carries its NULL flags."""
+    from tests.test_gpu_row_number import host_page_of, raw_output
+    from tests.test_gpu_small_pages import retained_pages
+    n = 5000
+    keys = np.arange(n, dtype=np.int64) % 97
+    host = Page([Block.bigint(keys), Block.double(np.arange(n, dtype=np.float64))], n)
+    bounds = [0, 700, 701, 2000, n]
+    build = list(range(0, 98, 2)) + [None]                               # 49 keys and a NULL
+    assert len(build) == 50
+    want = expected_marks(abi.BIGINT, build, keys.tolist())
+    assert set(want) == {True, None}
+    s, _builder = build_set(abi.BIGINT, build)
+    released = []
+    pages = retained_pages(host, bounds, released)
+    j = HashSemiJoinOperator(s, [abi.BIGINT, abi.DOUBLE], 0, output_mem=abi.MEM_DEVICE)
+    for i, p in enumerate(pages):
+        lo, hi = bounds[i], bounds[i + 1]
+        assert j.needsInput()
+        j.addInput(p)
+        assert released == list(range(i))                                # page i is still held
+        out = raw_output(j)
+        assert out is not None and out.mem == abi.MEM_DEVICE and out.position_count == hi - lo and out.channel_count == 3
+        got = host_page_of(j, out)                                       # reads the caller's blocks: they must still be intact
+        assert np.array_equal(got.blocks[0].values[:hi - lo], keys[lo:hi])
+        assert np.array_equal(got.blocks[1].values[:hi - lo], np.arange(lo, hi, dtype=np.float64))
+        assert got.blocks[2].to_pylist() == want[lo:hi]
+        assert released == list(range(i))                                # ... while its output page is out
+        j.needsInput()                                                   # the output page has been let go
+        assert released == list(range(i + 1))
+    j.finish()
+    j.close()
+    assert released == list(range(len(pages)))
+
+    # closed while an output page is still pending: the page goes back once, at close
+    released = []
+    pages = retained_pages(host, bounds, released)
+    j = HashSemiJoinOperator(s, [abi.BIGINT, abi.DOUBLE], 0, output_mem=abi.MEM_DEVICE)
+    j.addInput(pages[0])
+    assert not j.needsInput() and released == []
+    j.close()
+    assert released == [0]
+    del j
+    assert released == [0]
+
+
 # ---- sharing and lifetime --------------------------------------------------------------------------------------------------------
 def test_sharing_and_lifetimes(gpu):
     s = SetSupplier()
