@@ -65,15 +65,19 @@ typedef enum pa_type {
                       * digits is a PA_LONG_DECIMAL value), comparisons / BETWEEN / IN between operands of one type, negation, CAST
                       * from INTEGER / BIGINT / a decimal of smaller scale.  Aggregates: sum (-> DECIMAL(38, s), DecimalSumAggregation),
                       * avg (-> the input type, DecimalAverageAggregation: sum / count rounded half up), min / max / count.  Group key
-                      * of an aggregation: yes (ShortDecimalType: == of longs; $hashvalue = the value itself).  Join / sort keys and
-                      * payload channels of joins, sorts and exchanges: declare the channel PA_BIGINT -- the same LongArrayBlock, the same
-                      * == and < -- ; as the PARTITION key of an exchange it is not supported (its hash differs from BIGINT's) */
+                      * of an aggregation: yes (ShortDecimalType: == of longs; $hashvalue = the value itself).  Sort key of OrderBy /
+                      * TopN, join key, dynamic-filter channel (domains come back typed PA_DECIMAL), pa_hash_page channel and payload
+                      * channel of sorts and joins: yes, by the unscaled long.  Through the exchange and the page serde: not supported
+                      * (PA_ERR_NOT_SUPPORTED at pa_exchange_create / pa_page_serialize) */
     PA_LONG_DECIMAL = 9 /* LongDecimalType (.../type/LongDecimalType.java, UnscaledDecimal128Arithmetic.java): DECIMAL(p, s), 18 < p <= 38 --
                       * 16 B per position, little endian: the low 64 bits of the magnitude, then the high 63 bits with the SIGN in the
                       * top bit (sign-magnitude, as the reference's Slice holds it).  On the device path: a value inside expressions
                       * (products and sums of short decimals), the result of sum / avg over decimals, the sum half of their PARTIAL
-                      * state, an input of sum / avg / count, an operand of comparisons with its own type.  Not a key, not a min / max
-                      * input, not divided or rescaled down (PA_ERR_NOT_SUPPORTED).  Overflow: the reference's
+                      * state, an input of sum / avg / count, an operand of comparisons with its own type; a payload channel of
+                      * OrderBy, TopN and joins (16-byte elements), a pass-through channel, a pa_hash_page channel (XxHash64 of the low
+                      * long ^ XxHash64 of the high long).  Not a sort, join, group or dynamic-filter key, not a min / max input, not
+                      * divided or rescaled down, not through the exchange or the page serde (PA_ERR_NOT_SUPPORTED, from the factory
+                      * call).  Overflow: the reference's
                       * LongDecimalWithOverflow(AndLong)State carries an overflow counter through Step.PARTIAL, so a partial sum may pass
                       * 10^38 and come back (and avg over such sums is legal, DecimalAverageAggregation.average); the device state has no
                       * such counter and raises NUMERIC_VALUE_OUT_OF_RANGE as soon as a partial sum leaves +-10^38: the planner keeps

@@ -643,7 +643,8 @@ def topn(pages, n, sort_channels, sort_orders):
     TopNProcessor.java:35-110): the n first rows under SimplePageWithPositionComparator (…/SimplePageWithPositionComparator.java:
     45-70) with SortOrder.compareBlockValue (core/trino-spi/src/main/java/io/trino/spi/connector/SortOrder.java:58-84), as
     rows.  Fully tied rows keep arrival order here (the reference leaves it open).  Type orders: BIGINT / INTEGER / DATE
-    numeric, DOUBLE Double.compare (-0.0 < 0.0, NaN last), VARCHAR unsigned bytes (Slice.compareTo), BOOLEAN false < true."""
+    numeric, DECIMAL / LONG_DECIMAL by unscaled value (one scale per channel), DOUBLE / REAL Double.compare (-0.0 < 0.0, NaN last),
+    VARCHAR unsigned bytes (Slice.compareTo), BOOLEAN false < true."""
     import functools
     import math
     import struct

@@ -300,6 +300,16 @@ static int64_t val_hash(const orc_val* v)
             return (int64_t)orc_xxh64(v->s, v->slen, 0);
         case PA_DECIMAL: /* SPI/type/ShortDecimalType.java:127-131: hashCodeOperator(long value) = value */
             return v->i;
+        case PA_LONG_DECIMAL: { /* SPI/type/LongDecimalType.java:164-179: no HASH_CODE operator, so TypeOperators (SPI/type/
+                                 * TypeOperators.java:228-233) hands out XX_HASH_64 = XxHash64.hash(low) ^ XxHash64.hash(high), the two
+                                 * longs of the Slice as they are stored (sign in the top bit of the high long) */
+            uint8_t words[16];
+            uint64_t lo, hi;
+            ld_write(words, v->q);
+            memcpy(&lo, words, 8);
+            memcpy(&hi, words + 8, 8);
+            return (int64_t)(orc_xxh64(&lo, 8, 0) ^ orc_xxh64(&hi, 8, 0));
+        }
         default:
             return 0;
     }
@@ -1344,6 +1354,7 @@ static orc_val builder_get(const col_builder* b, int32_t pos)
         case PA_REAL: v.d = (double)((float*)b->values)[pos]; break;
         case PA_BOOLEAN: v.i = b->values[pos]; break;
         case PA_DECIMAL: v.i = ((int64_t*)b->values)[pos]; v.q = v.i; break;
+        case PA_LONG_DECIMAL: v.q = ld_read(b->values + 16 * (size_t)pos); break;
         case PA_VARCHAR:
             v.s = b->values + b->offsets[pos];
             v.slen = b->offsets[pos + 1] - b->offsets[pos];
@@ -2036,6 +2047,10 @@ static int equals_ignore_nulls(const orc_val* a, const orc_val* b)
         case PA_REAL: /* SPI/type/RealType.java:101-105 */
             return a->d == b->d;
         case PA_VARCHAR: return a->slen == b->slen && (a->slen == 0 || memcmp(a->s, b->s, (size_t)a->slen) == 0);
+        case PA_DECIMAL:
+        case PA_LONG_DECIMAL: /* SPI/type/LongDecimalType.java:139-162: both longs equal -- the same as equal unscaled values for the
+                               * canonical Slices ld_write produces (a zero magnitude never carries the sign) */
+            return a->q == b->q;
         default: return a->i == b->i;
     }
 }

@@ -14,7 +14,8 @@ namespace {
 __device__ __forceinline__ u64 df_key(int type, const void* values, i64 r)
 {
     switch (type) {
-        case PA_BIGINT: return (u64)((const i64*)values)[r];
+        case PA_BIGINT:
+        case PA_DECIMAL: return (u64)((const i64*)values)[r];  // a short decimal is its unscaled long: no bit pattern of it is special
         case PA_INTEGER:
         case PA_DATE: return (u64)(i64)((const i32*)values)[r];
         case PA_BOOLEAN: return ((const u8*)values)[r] != 0 ? 1ULL : 0ULL;
@@ -24,11 +25,12 @@ __device__ __forceinline__ u64 df_key(int type, const void* values, i64 r)
             const u64 b = (u64)__double_as_longlong((double)f);
             return b == 0x8000000000000000ULL ? 0ULL : b;
         }
-        default: {  // DOUBLE
+        case PA_DOUBLE: {  // one NaN, +0.0 for both zeros
             const u64 b = ((const u64*)values)[r];
             if ((b & 0x7fffffffffffffffULL) > 0x7ff0000000000000ULL) return 0x7ff8000000000000ULL;
             return b == 0x8000000000000000ULL ? 0ULL : b;
         }
+        default: return 0ULL;  // not reached: launch_df_collect refuses every other type
     }
 }
 
@@ -162,6 +164,16 @@ size_t df_partials_bytes() { return (size_t)kDfBlocks * 3 * 8; }
 void launch_df_collect(int32_t type, const void* values, const uint8_t* nulls, int64_t n, const DfSet* set, int64_t* partials, int64_t* running,
                        hipStream_t s)
 {
+    switch (type) {
+        case PA_BIGINT:
+        case PA_INTEGER:
+        case PA_DATE:
+        case PA_BOOLEAN:
+        case PA_REAL:
+        case PA_DOUBLE:
+        case PA_DECIMAL: break;
+        default: throw Error(PA_ERR_NOT_SUPPORTED, "dynamic filter over a channel type without a 64-bit key");
+    }
     if (n <= 0) return;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, kDfBlocks));
     DfSet none{};

@@ -1,7 +1,8 @@
 // keyed_operator.hpp -- what the operators over a key table share on the host: MarkDistinct / DistinctLimit (op_distinct.cpp),
-// SetBuilder / HashSemiJoin (op_semi_join.cpp), RowNumber (op_row_number.cpp), TopNRanking (op_topn_ranking.cpp).
+// SetBuilder / HashSemiJoin (op_semi_join.cpp), RowNumber (op_row_number.cpp), TopNRanking (op_topn_ranking.cpp).  The type checks
+// also serve the operators that sort, join or collect by a channel (op_order_by.cpp, op_topn.cpp, op_join.cpp, op_dynamic_filter.cpp).
 //
-//   descriptor checks    check_key_type, check_input_channels, check_channels, check_key_channels, check_hash_channel, check_output_mem
+//   descriptor checks    check_key_type, check_carried_type, check_input_channels, check_channels, check_key_channels, check_hash_channel, check_output_mem
 //   the key table        make_distinct_hash, KeyColumns, bits_for, grow_by_group_id
 //   KeepCompactor        keep marks -> rows kept per block -> scan -> positions (one read-back)
 //   PassThroughOutput    "the input page's channels with one computed column behind them": the retained input page, the zero-copy
@@ -23,7 +24,8 @@ namespace pa {
 
 // ---- descriptor checks: before the device is asked for, so a shape the device path does not take is reported as such with or
 // without a GPU.  Where a descriptor has two defects the first check decides the status: every operator keeps its own order. -----------
-// the key types the canonical 64-bit word covers (kernels/pa_canon.h); `what`: "distinct", "partition", "semi-join"
+// the key types the canonical 64-bit word covers (kernels/pa_canon.h) -- also the types with an order-preserving image
+// (topn_kernels.hip), a join equality (join_kernels.hip) and a dynamic-filter key; `what`: "distinct", "partition", "semi-join", "sort", "join"
 inline void check_key_type(int32_t type, const char* what)
 {
     switch (type) {
@@ -38,6 +40,24 @@ inline void check_key_type(int32_t type, const char* what)
         case PA_LONG_DECIMAL:
         case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, std::string(what) + " key type not supported on the device");
         default: throw Error(PA_ERR_INVALID_ARGUMENT, std::string("unknown ") + what + " key type");
+    }
+}
+// a channel an operator only carries -- copied position by position, never compared or hashed: every flat or variable-width type
+// (LONG_DECIMAL as 16-byte elements); `what`: "output", "payload", "pass-through"
+inline void check_carried_type(int32_t type, const char* what)
+{
+    switch (type) {
+        case PA_BIGINT:
+        case PA_INTEGER:
+        case PA_DATE:
+        case PA_DOUBLE:
+        case PA_REAL:
+        case PA_BOOLEAN:
+        case PA_VARCHAR:
+        case PA_DECIMAL:
+        case PA_LONG_DECIMAL: return;
+        case PA_ROW: throw Error(PA_ERR_NOT_SUPPORTED, std::string(what) + " channel type not supported on the device");
+        default: throw Error(PA_ERR_INVALID_ARGUMENT, std::string("unknown ") + what + " channel type");
     }
 }
 inline void check_input_channels(int32_t channels) { PA_REQUIRE(channels > 0 && channels <= 64, PA_ERR_NOT_SUPPORTED, "1..64 input channels"); }

@@ -13,6 +13,7 @@
 
 #include "dynfilter_kernels.hpp"
 #include "intern_kernels.hpp"
+#include "keyed_operator.hpp"
 #include "operator.hpp"
 
 namespace pa {
@@ -81,6 +82,13 @@ public:
         PA_REQUIRE(d->max_distinct_values >= 0 && d->max_distinct_values <= (1 << 24), PA_ERR_NOT_SUPPORTED,
                    "max_distinct_values above 2^24 is not on the device path");
         types_.assign(d->input_types, d->input_types + d->input_channel_count);
+        // what the device path does not take, said before a page arrives: a filter channel needs a 64-bit key (or the string
+        // dictionary), every channel must pass through as the caller's own block
+        for (int i = 0; i < d->filter_channel_count; i++) {
+            PA_REQUIRE(d->filter_channels[i] >= 0 && d->filter_channels[i] < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "filter channel out of range");
+            check_key_type(types_[(size_t)d->filter_channels[i]], "dynamic filter");
+        }
+        for (int32_t t : types_) check_carried_type(t, "pass-through");
         max_distinct_ = d->max_distinct_values;
         max_bytes_ = d->max_filter_size_bytes;
         row_limit_ = d->min_max_collection_limit;

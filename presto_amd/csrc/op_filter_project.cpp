@@ -175,6 +175,8 @@ FpSpec make_fp_join_spec(const pa_filter_project_desc* fp, const pa_lookup_join_
     for (int col : ls.output_channels) {
         const int32_t t = ls.cols[(size_t)col].type;
         PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "VARCHAR build columns are not carried by the fused probe");
+        // (said here, not by the code generator at the first page: the operator chain carries them)
+        PA_REQUIRE(t != PA_DECIMAL && t != PA_LONG_DECIMAL, PA_ERR_NOT_SUPPORTED, "DECIMAL build columns are not carried by the fused probe");
         PA_REQUIRE((int)js->build_cols.size() < kMaxBuildChannels, PA_ERR_NOT_SUPPORTED, "the fused probe carries at most 8 build columns");
         OwnedExpr e;
         pa_expr_node node{};

@@ -26,12 +26,20 @@ bool lookup_source_unique_keyed(pa_lookup_source* ls)
 
 namespace {
 
+// a ROW channel has no place in a probe page on the device: said by the factory call, whichever execution would have met it
+void refuse_row_channels(const pa_filter_project_desc& fp)
+{
+    for (int32_t c = 0; fp.input_types != nullptr && c < fp.input_channel_count; c++)
+        PA_REQUIRE(fp.input_types[c] != PA_ROW, PA_ERR_NOT_SUPPORTED, "ROW probe channels are not supported on the device");
+}
+
 class FusedJoinAggregationOperator : public pa_operator {
 public:
     // FilterAndProject -> LookupJoin (no aggregation behind it)
     FusedJoinAggregationOperator(const pa_fused_join_desc* d, pa_lookup_source* bridge) : bridge_(*bridge)
     {
         PA_REQUIRE(bridge->impl != nullptr, PA_ERR_ILLEGAL_STATE, "lookup source has no build operator yet");
+        refuse_row_channels(d->filter_project);
         PA_REQUIRE(d->join.join_type == PA_JOIN_INNER && d->join.filter == nullptr, PA_ERR_NOT_SUPPORTED, "the fused join is an inner join without a filter function");
         void* stream = shared_stream(d->join.stream ? d->join.stream : d->filter_project.stream);
         pa_filter_project_desc fp = d->filter_project;
@@ -61,6 +69,7 @@ public:
     FusedJoinAggregationOperator(const pa_fused_join_aggregation_desc* d, pa_lookup_source* bridge) : bridge_(*bridge)
     {
         PA_REQUIRE(bridge->impl != nullptr, PA_ERR_ILLEGAL_STATE, "lookup source has no build operator yet");
+        refuse_row_channels(d->filter_project);
         PA_REQUIRE(d->join.join_type == PA_JOIN_INNER, PA_ERR_NOT_SUPPORTED, "the fused join-aggregation is an inner join");
         void* stream = shared_stream(d->aggregation.stream ? d->aggregation.stream : (d->join.stream ? d->join.stream : d->filter_project.stream));
         // the chain: intermediate pages stay in HBM, everything on one stream

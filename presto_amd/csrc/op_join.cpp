@@ -20,6 +20,7 @@
 #include "exchange_kernels.hpp"
 #include "join_kernels.hpp"
 #include "join_source.hpp"
+#include "keyed_operator.hpp"
 #include "operator.hpp"
 #include "scan_kernels.hpp"
 #include "static_kernels.hpp"
@@ -84,6 +85,10 @@ public:
             PA_REQUIRE(d->output_channels[i] >= 0 && d->output_channels[i] < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "output channel out of range");
             ls_->output_channels.push_back(d->output_channels[i]);
         }
+        // what the device path does not take, said here and not at the probe: a join channel needs a hash and an equality, every
+        // build channel (all of them are kept, PagesIndex.addPage) a copy by position
+        for (int c : ls_->join_channels) check_key_type(d->input_types[c], "join");
+        for (int c = 0; c < d->input_channel_count; c++) check_carried_type(d->input_types[c], "build");
         ls_->hash_channel = d->hash_channel;
         PA_REQUIRE(ls_->hash_channel < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
         PA_REQUIRE(ls_->hash_channel < 0 || d->input_types[ls_->hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
@@ -497,6 +502,7 @@ public:
         for (int i = 0; i < d->probe_output_channel_count; i++) {
             int c = d->probe_output_channels[i];
             PA_REQUIRE(c >= 0 && c < n_probe_channels_, PA_ERR_INVALID_ARGUMENT, "probe output channel out of range");
+            check_carried_type(probe_types_[c], "probe output");
             output_channels_.push_back(c);
         }
         output_mem_ = d->output_mem;
@@ -702,7 +708,7 @@ public:
         gm.count = total_out;
         auto flat = [&](int32_t type, const void* values, const uint8_t* nulls, int which, bool null_rows, OutColumn& out) {
             const int w = type_width(type);
-            if ((w != 1 && w != 4 && w != 8) || gm.ncols >= GATHER_MULTI_MAX_COLS) return false;
+            if ((w != 1 && w != 4 && w != 8 && w != 16) || gm.ncols >= GATHER_MULTI_MAX_COLS) return false;
             out.type = type;
             out.varwidth = false;
             out.is_view = false;
@@ -1070,6 +1076,7 @@ public:
         for (int i = 0; i < d->probe_output_channel_count; i++) {
             int c = d->probe_output_channels[i];
             PA_REQUIRE(c >= 0 && c < d->probe_channel_count, PA_ERR_INVALID_ARGUMENT, "probe output channel out of range");
+            check_carried_type(d->probe_types[c], "probe output");
             probe_output_types_.push_back(d->probe_types[c]);
         }
         output_mem_ = d->output_mem;

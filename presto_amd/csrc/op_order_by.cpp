@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "keyed_operator.hpp"
 #include "operator.hpp"
 #include "scan_kernels.hpp"
 #include "sort_kernels.hpp"
@@ -53,6 +54,10 @@ public:
             PA_REQUIRE(sort_channels_[i] >= 0 && sort_channels_[i] < (int)types_.size(), PA_ERR_INVALID_ARGUMENT, "sort channel out of range");
             PA_REQUIRE(sort_orders_[i] >= 0 && sort_orders_[i] <= 3, PA_ERR_INVALID_ARGUMENT, "unknown sort order");
         }
+        // what the device path does not take, said before a row arrives: a sort channel needs an order-preserving image, an output
+        // channel a copy by position (channels that are neither are never read)
+        for (int c : sort_channels_) check_key_type(types_[(size_t)c], "sort");
+        for (int c : output_channels_) check_carried_type(types_[(size_t)c], "output");
         output_mem_ = d->output_mem;
         cols_.resize(types_.size());
         needed_.assign(types_.size(), false);
@@ -402,13 +407,10 @@ public:
                 launch_topn_values_of_keys(a.type, sorted_images, n, first_descending, oc.values.ensure((size_t)n * type_width(a.type)), s);
             }
             else {
-                const int w = type_width(a.type);
-                if (w == 1 || w == 4 || w == 8) {
-                    gc.src = a.values.ptr();
-                    gc.dst = oc.values.ensure((size_t)n * w);
-                    gc.width = w;
-                }
-                else launch_gather_flat(a.values.ptr(), w, perm, n, oc.values.ensure((size_t)n * w), s);   // (LONG_DECIMAL: 16 bytes)
+                const int w = type_width(a.type);   // (1, 4, 8, or 16 for a LONG_DECIMAL: the constructor refused every other type)
+                gc.src = a.values.ptr();
+                gc.dst = oc.values.ensure((size_t)n * w);
+                gc.width = w;
             }
             if (nulls) {
                 gc.src_nulls = nulls;

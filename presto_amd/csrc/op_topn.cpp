@@ -13,6 +13,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "keyed_operator.hpp"
 #include "operator.hpp"
 #include "scan_kernels.hpp"
 #include "topn_kernels.hpp"
@@ -43,6 +44,10 @@ public:
             PA_REQUIRE(sort_channels_[i] >= 0 && sort_channels_[i] < (int)types_.size(), PA_ERR_INVALID_ARGUMENT, "sort channel out of range");
             PA_REQUIRE(sort_orders_[i] >= 0 && sort_orders_[i] <= 3, PA_ERR_INVALID_ARGUMENT, "unknown sort order");
         }
+        // what the device path does not take, said before a row arrives: a sort channel needs an order-preserving image and a host
+        // comparison, every channel (all of them go out) a copy by position
+        for (int32_t c : sort_channels_) check_key_type(types_[(size_t)c], "sort");
+        for (int32_t t : types_) check_carried_type(t, "payload");
         n_ = d->n;
         output_mem_ = d->output_mem;
         store_.resize(types_.size());
@@ -422,7 +427,8 @@ private:
     static int compare_values(const HostColumn& hc, int64_t a, int64_t b)
     {
         switch (hc.type) {
-            case PA_BIGINT: {
+            case PA_BIGINT:
+            case PA_DECIMAL: {  // ShortDecimalType.comparisonOperator: the unscaled longs
                 int64_t x, y;
                 memcpy(&x, &hc.values[(size_t)a * 8], 8);
                 memcpy(&y, &hc.values[(size_t)b * 8], 8);
@@ -469,7 +475,7 @@ private:
                 if (c != 0) return c < 0 ? -1 : 1;
                 return al < bl ? -1 : (al > bl ? 1 : 0);
             }
-            default: return 0;
+            default: throw Error(PA_ERR_NOT_SUPPORTED, "internal: sort channel type without a host comparison");  // (refused at creation)
         }
     }
 

@@ -20,6 +20,10 @@ static inline int grid_for(int64_t work, int block, int max_blocks = 256 * 8)
 // ---------------------------------------------------------------------------------------------
 // Block.copyPositions / dictionary decode
 // ---------------------------------------------------------------------------------------------
+// a 16-byte element (LongDecimalType: two longs per position); 8-byte aligned like the longs a caller's block holds
+struct u64x2 {
+    u64 lo, hi;
+};
 template <typename T>
 __global__ __launch_bounds__(256) void k_gather(const T* __restrict__ src, const i32* __restrict__ pos, i64 n, T* __restrict__ dst)
 {
@@ -40,7 +44,7 @@ __global__ __launch_bounds__(256) void k_gather_or_null(const T* __restrict__ sr
 {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
         const i32 p = pos[i];
-        if (dst) dst[i] = p < 0 ? (T)0 : src[p];
+        if (dst) dst[i] = p < 0 ? T{} : src[p];
         dst_nulls[i] = p < 0 ? (u8)1 : (src_nulls ? src_nulls[p] : (u8)0);
     }
 }
@@ -50,11 +54,12 @@ void launch_gather_or_null(const void* src, int elem_bytes, const uint8_t* src_n
     if (count <= 0) return;
     int g = grid_for(count, 256);
     switch (elem_bytes) {
+        case 16: hipLaunchKernelGGL(k_gather_or_null<u64x2>, g, 256, 0, s, (const u64x2*)src, src_nulls, positions, count, (u64x2*)dst, dst_nulls); break;
         case 8: hipLaunchKernelGGL(k_gather_or_null<u64>, g, 256, 0, s, (const u64*)src, src_nulls, positions, count, (u64*)dst, dst_nulls); break;
         case 4: hipLaunchKernelGGL(k_gather_or_null<u32>, g, 256, 0, s, (const u32*)src, src_nulls, positions, count, (u32*)dst, dst_nulls); break;
         case 1: hipLaunchKernelGGL(k_gather_or_null<u8>, g, 256, 0, s, (const u8*)src, src_nulls, positions, count, (u8*)dst, dst_nulls); break;
         case 0: hipLaunchKernelGGL(k_gather_or_null<u8>, g, 256, 0, s, (const u8*)nullptr, src_nulls, positions, count, (u8*)nullptr, dst_nulls); break;
-        default: throw Error(PA_ERR_INVALID_ARGUMENT, "unsupported element width");
+        default: throw Error(PA_ERR_NOT_SUPPORTED, "gather: unsupported element width");
     }
     PA_HIP(hipGetLastError());
 }
@@ -64,10 +69,11 @@ void launch_gather_flat(const void* src, int elem_bytes, const int32_t* position
     if (count <= 0) return;
     int g = grid_for(count, 256);
     switch (elem_bytes) {
+        case 16: hipLaunchKernelGGL(k_gather<u64x2>, g, 256, 0, s, (const u64x2*)src, positions, count, (u64x2*)dst); break;
         case 8: hipLaunchKernelGGL(k_gather<u64>, g, 256, 0, s, (const u64*)src, positions, count, (u64*)dst); break;
         case 4: hipLaunchKernelGGL(k_gather<u32>, g, 256, 0, s, (const u32*)src, positions, count, (u32*)dst); break;
         case 1: hipLaunchKernelGGL(k_gather<u8>, g, 256, 0, s, (const u8*)src, positions, count, (u8*)dst); break;
-        default: throw Error(PA_ERR_INVALID_ARGUMENT, "gather: unsupported element width");
+        default: throw Error(PA_ERR_NOT_SUPPORTED, "gather: unsupported element width");
     }
     PA_HIP(hipGetLastError());
 }
@@ -84,8 +90,10 @@ __global__ __launch_bounds__(256) void k_gather_multi(GatherMultiArgs a)
             const GatherMultiCol col = a.col[c];
             const i32 p = col.which ? p1 : p0;
             if (col.dst) {
+                // (widths 1, 4, 8, 16 only: launch_gather_multi refuses every other)
                 if (col.width == 8) ((u64*)col.dst)[i] = p < 0 ? 0ULL : ((const u64*)col.src)[p];
                 else if (col.width == 4) ((u32*)col.dst)[i] = p < 0 ? 0u : ((const u32*)col.src)[p];
+                else if (col.width == 16) ((u64x2*)col.dst)[i] = p < 0 ? u64x2{} : ((const u64x2*)col.src)[p];
                 else ((u8*)col.dst)[i] = p < 0 ? (u8)0 : ((const u8*)col.src)[p];
             }
             if (col.dst_nulls) col.dst_nulls[i] = p < 0 ? (u8)1 : (col.src_nulls ? col.src_nulls[p] : (u8)0);
@@ -95,6 +103,10 @@ __global__ __launch_bounds__(256) void k_gather_multi(GatherMultiArgs a)
 void launch_gather_multi(const GatherMultiArgs& args, hipStream_t s)
 {
     if (args.count <= 0 || args.ncols <= 0) return;
+    for (int c = 0; c < args.ncols; c++) {
+        const int w = args.col[c].width;
+        PA_REQUIRE(args.col[c].dst == nullptr || w == 1 || w == 4 || w == 8 || w == 16, PA_ERR_NOT_SUPPORTED, "gather: unsupported element width");
+    }
     hipLaunchKernelGGL(k_gather_multi, grid_for(args.count, 256), 256, 0, s, args);
     PA_HIP(hipGetLastError());
 }
@@ -651,7 +663,15 @@ __global__ __launch_bounds__(256) void k_hash_page(HashPageArgs a)
                         h = (i64)pa_xxh64((const u8*)col.values + o, col.offsets[r + 1] - o);
                         break;
                     }
-                    default: break;
+                    case PA_DECIMAL: h = ((const i64*)col.values)[r]; break;  // ShortDecimalType.hashCodeOperator: the unscaled value itself
+                    case PA_LONG_DECIMAL: {
+                        // LongDecimalType has no hash code operator of its own: TypeOperators falls back to its XX_HASH_64,
+                        // XxHash64.hash(low) ^ XxHash64.hash(high) over the two longs as they are stored
+                        const u64* w = (const u64*)col.values + 2 * r;
+                        h = (i64)(pa_xxh64_long(w[0]) ^ pa_xxh64_long(w[1]));
+                        break;
+                    }
+                    default: break;  // not reached: launch_hash_page refuses every other type
                 }
             }
             result = pa_combine_hash(result, h);
@@ -662,6 +682,11 @@ __global__ __launch_bounds__(256) void k_hash_page(HashPageArgs a)
 
 void launch_hash_page(const HashPageArgs& args, hipStream_t s)
 {
+    for (int c = 0; c < args.ncols; c++) {
+        const int32_t t = args.col[c].type;
+        PA_REQUIRE((t >= PA_BIGINT && t <= PA_VARCHAR) || t == PA_REAL || t == PA_DECIMAL || t == PA_LONG_DECIMAL, PA_ERR_NOT_SUPPORTED,
+                   "hash of a channel type without a hash operator on the device");
+    }
     if (args.n <= 0) return;
     hipLaunchKernelGGL(k_hash_page, grid_for(args.n, 256), 256, 0, s, args);
     PA_HIP(hipGetLastError());

@@ -56,7 +56,7 @@ struct GatherMultiCol {
     const uint8_t* src_nulls;
     void* dst;
     uint8_t* dst_nulls;   // written when non-null (a -1 position gives 1)
-    int32_t width;        // 1, 4 or 8
+    int32_t width;        // 1, 4, 8 or 16 (LONG_DECIMAL)
     int32_t which;
 };
 struct GatherMultiArgs {

@@ -32,7 +32,10 @@ __device__ __forceinline__ u64 row_key(i32 type, const void* __restrict__ values
     u64 img = 0;
     if (!is_null) {
         switch (type) {
-            case PA_BIGINT: img = (u64)((const i64*)values)[i] ^ 0x8000000000000000ULL; break;
+            case PA_BIGINT:
+            case PA_DECIMAL:  // ShortDecimalType.comparisonOperator: the unscaled longs (one scale per channel)
+                img = (u64)((const i64*)values)[i] ^ 0x8000000000000000ULL;
+                break;
             case PA_INTEGER:
             case PA_DATE: img = (u64)(i64)((const i32*)values)[i] ^ 0x8000000000000000ULL; break;
             case PA_BOOLEAN: img = ((const u8*)values)[i] ? 1ULL : 0ULL; break;
@@ -57,7 +60,7 @@ __device__ __forceinline__ u64 row_key(i32 type, const void* __restrict__ values
                 for (int b = 0; b < 8; b++) img = (img << 8) | (b < len ? (u64)p[b] : 0ULL);
                 break;
             }
-            default: break;
+            default: break;  // not reached: require_image_type below refuses every other type before a launch
         }
     }
     return order_key(img, is_null, sort_order);
@@ -396,6 +399,23 @@ __global__ __launch_bounds__(256) void k_topn_state_partition(const u8* __restri
 
 int grid_of(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 2048)); }
 
+// the types row_key has an image for (the kernels carry no error word: every launch that takes a type asks here first)
+void require_image_type(int32_t type)
+{
+    switch (type) {
+        case PA_TOPN_KEYS:
+        case PA_BIGINT:
+        case PA_INTEGER:
+        case PA_DATE:
+        case PA_DOUBLE:
+        case PA_REAL:
+        case PA_BOOLEAN:
+        case PA_VARCHAR:
+        case PA_DECIMAL: return;
+        default: throw Error(PA_ERR_NOT_SUPPORTED, "sort channel type has no order-preserving image on the device");
+    }
+}
+
 }  // namespace
 
 void launch_topn_state(const uint64_t* keys, int64_t n, uint64_t threshold, bool first, uint8_t* state, hipStream_t s)
@@ -433,6 +453,7 @@ void launch_topn_state_partition(const uint8_t* state, const int32_t* tie_rank, 
 void launch_topn_keys(int32_t type, const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int32_t sort_order,
                       uint64_t* keys, hipStream_t s)
 {
+    require_image_type(type);
     if (n <= 0) return;
     hipLaunchKernelGGL(k_topn_keys, grid_of(n), 256, 0, s, type, values, (const i32*)offsets, (const u8*)nulls, (i64)n, sort_order, (u64*)keys);
     PA_HIP(hipGetLastError());
@@ -441,6 +462,7 @@ void launch_topn_keys(int32_t type, const void* values, const int32_t* offsets, 
 int launch_topn_keys_or_and(int32_t type, const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int32_t sort_order, uint64_t* keys,
                             uint64_t* or_and, hipStream_t s)
 {
+    require_image_type(type);
     if (n <= 0) return 0;
     const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, kKeysOrAndBlocks));
     hipLaunchKernelGGL(k_topn_keys_or_and, blocks, 256, 0, s, type, values, (const i32*)offsets, (const u8*)nulls, (i64)n, sort_order, (u64*)keys, (u64*)or_and);
@@ -470,6 +492,7 @@ void launch_topn_values_of_keys(int32_t type, const uint64_t* keys, int64_t n, b
 void launch_topn_sample_bound(int32_t type, const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int32_t sort_order,
                               int64_t sample_rows, int64_t rank, uint64_t* sample_keys, uint64_t* bound_out, hipStream_t s)
 {
+    require_image_type(type);
     PA_REQUIRE(sample_rows >= 1 && sample_rows <= kSelectSmall && rank >= 1 && rank <= sample_rows && n >= sample_rows, PA_ERR_INVALID_ARGUMENT,
                "bad TopN sample");
     const int64_t stride = n / sample_rows;
@@ -488,6 +511,7 @@ void launch_topn_sample_bound(int32_t type, const void* values, const int32_t* o
 void launch_topn_filter(int32_t type, const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int32_t sort_order, uint64_t bound,
                         const uint64_t* device_bound, uint32_t capacity, int32_t* out_positions, uint64_t* out_keys, uint32_t* counter, hipStream_t s)
 {
+    require_image_type(type);
     PA_HIP(hipMemsetAsync(counter, 0, 8, s));
     if (n <= 0) return;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 511) / 512, 4096));

@@ -514,7 +514,9 @@ class DynamicFilterSourceOperator(Operator):
 
     def predicate(self):
         """What dynamicPredicateConsumer received: None while it has not been called, "all" for TupleDomain.all(), else one
-        entry per filter channel: ("all",) | ("none",) | ("values", [..ascending..]) | ("range", low, high)."""
+        entry per filter channel: ("all",) | ("none",) | ("values", [..ascending..]) | ("range", low, high).  `domain_types` then holds
+        the pa_type of each entry's value column (None for an entry without values)."""
+        self.domain_types = None
         is_all = C.c_int32()
         doms = (abi.pa_domain * self._filters)()
         if not check(lib().pa_dynamic_filter_poll(self._h, C.byref(is_all), doms, self._filters)):
@@ -522,6 +524,7 @@ class DynamicFilterSourceOperator(Operator):
         if is_all.value:
             return "all"
         out = []
+        self.domain_types = [None if d.kind in (abi.DOMAIN_ALL, abi.DOMAIN_NONE) else d.values.type for d in doms]
         for d in doms:
             if d.kind == abi.DOMAIN_ALL:
                 out.append(("all",))

@@ -116,3 +116,38 @@ def test_lz4_block_format_hand_computed(oracle):
     assert oracle.lz4_decompress(block, 273) == bytes(range(256)) + bytes(range(17))
     for data in (b"", b"x", b"0123456789ab", b"abcd" * 100, bytes(range(256)) * 3, b"\0" * 5000):
         assert oracle.lz4_decompress(oracle.lz4_compress(data), len(data)) == data
+
+
+def test_long_decimal_hash_hand_computed(oracle):
+    """LongDecimalType declares no HASH_CODE operator (core/trino-spi/src/main/java/io/trino/spi/type/LongDecimalType.java:164-179), so
+    TypeOperators (…/TypeOperators.java:228-233) hands out its XX_HASH_64: XxHash64.hash(low) ^ XxHash64.hash(high) over the two longs of
+    the Slice -- low 64 bits of the magnitude, then the high 63 bits with the sign on top.  Worked by hand from the public XXH64 values of
+    the longs 0, 1 and -2^63 (tests/golden/xxh64_vectors.json):
+        0     = (0, 0)        ->  34c96acdcadb1bbb ^ 34c96acdcadb1bbb = 0
+        1     = (1, 0)        ->  9f29cb17a2a49995 ^ 34c96acdcadb1bbb = abe0a1da687f822e
+        -1    = (1, 2^63)     ->  9f29cb17a2a49995 ^ 3f425eacf01544e0 = a06b95bb52b1dd75
+        2^64  = (0, 1)        ->  the hash of 1 again: the XOR does not tell the halves apart
+    NULL hashes to 0 like every type; in a row hash the value's hash is combined as 31 * h + it."""
+    values = [0, 1, -1, 1 << 64, None, 10 ** 38 - 1, -(10 ** 38 - 1)]
+    page = Page([Block.long_decimal(values), Block.bigint([7] * len(values))], len(values))
+    got = [h & M for h in oracle.hash_page(page, [0]).tolist()]
+    assert got[:5] == [0, 0xABE0A1DA687F822E, 0xA06B95BB52B1DD75, 0xABE0A1DA687F822E, 0]
+    for v, h in zip(values[5:], got[5:]):   # +-(10^38 - 1): both words in use
+        mag = abs(v)
+        assert h == (oracle.xxh64_long(mag & M) ^ oracle.xxh64_long((mag >> 64) | ((1 << 63) if v < 0 else 0))) & M
+    both = oracle.hash_page(page, [0, 1]).tolist()
+    assert both == [s64(31 * s64(h) + py_hash_bigint(7)) for h in got]
+
+
+def test_long_decimal_join_keys_compare_by_value(oracle):
+    """positionEqualsRowIgnoreNulls over a LONG_DECIMAL key (LongDecimalType.java:139-162: both longs equal): values that share the low
+    word, the high word or the magnitude are different keys; NULL matches nothing."""
+    big = 0x0123456789ABCDEF0123
+    build = [big, -big, big + (1 << 64), 5, None, big]
+    probe = [big, -big, big + (1 << 64), 5, None, big + 1, -5]
+    j = oracle.HashJoin([abi.LONG_DECIMAL, abi.BIGINT], [0], [1])
+    j.add_build_page(Page([Block.long_decimal(build), Block.bigint(list(range(len(build))))], len(build)))
+    j.build()
+    joined, _, _ = j.probe(Page([Block.long_decimal(probe), Block.bigint([10 * i for i in range(len(probe))])], len(probe)),
+                           [abi.LONG_DECIMAL, abi.BIGINT], [0], [0, 1])
+    assert joined.to_rows() == [(big, 0, 5), (big, 0, 0), (-big, 10, 1), (big + (1 << 64), 20, 2), (5, 30, 3)]
