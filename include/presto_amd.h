@@ -545,6 +545,76 @@ typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingTy
     void* stream;
 } pa_topn_ranking_desc;
 
+/* WindowOperator, the ranking functions: `row_number() / rank() / dense_rank() / percent_rank() / cume_dist() / ntile(b) OVER (PARTITION
+ * BY k ... ORDER BY x ...)`, planned by LocalExecutionPlanner.visitWindow (WindowOperator.java over RegularWindowPartition and the
+ * functions of operator/window/).  These six ignore frames.  Value functions (lag, lead, first_value, last_value, nth_value), aggregate
+ * window functions, frames, pre-grouped / pre-sorted input, spill and pattern recognition have no id here: the caller keeps the
+ * reference operator for a window node that uses one.
+ *   Order: the rows are sorted by SimplePageWithPositionComparator over [partition channels, each ASC_NULLS_LAST] + [sort channels with
+ *     their orders] (WindowOperator.java:294), under the rules of pa_order_by_desc.  Rows that compare equal on all of those channels
+ *     stay in arrival order (the reference's sort leaves this open; it is what TopN, OrderBy and TopNRanking promise here too).
+ *   Partitions: a new partition starts at sorted row 0 and at every sorted row that IS DISTINCT FROM its predecessor on some partition
+ *     channel: NULL equals NULL, any NaN equals any NaN, -0.0 equals +0.0, VARCHAR by bytes, BOOLEAN zero / non-zero.  With one
+ *     partition channel these are pa_row_number_desc's partitions, in ascending order with the NULL partition last.  No partition
+ *     channels: one partition.
+ *   Peers: a new peer group starts at a partition start and at every row that IS DISTINCT FROM its predecessor on some sort channel,
+ *     under the same rules (RegularWindowPartition.java:180-190).  -0.0 and +0.0 in a sort channel ARE peers here, as in the reference
+ *     -- unlike PA_RANKING_RANK of pa_topn_ranking_desc, where the comparator decides and they are not.  No sort channels: the whole
+ *     partition is one peer group.
+ *   Functions: with i the row's 0-based place in its partition, N the partition's size, [ps, pe) its peer group's places and d the
+ *     number of peer groups up to and including its own:
+ *       PA_WINDOW_ROW_NUMBER    i + 1                                          BIGINT
+ *       PA_WINDOW_RANK          ps + 1                                         BIGINT
+ *       PA_WINDOW_DENSE_RANK    d                                              BIGINT
+ *       PA_WINDOW_PERCENT_RANK  N == 1 ? 0.0 : (double)ps / (double)(N - 1)    DOUBLE
+ *       PA_WINDOW_CUME_DIST     (double)pe / (double)N                         DOUBLE
+ *       PA_WINDOW_NTILE         bucket + 1 (NTileFunction.bucket, below)       BIGINT
+ *     The first five take no argument (argument_count 0) and never produce NULL; the DOUBLE results are one IEEE division of two exactly
+ *     converted integers.  ntile takes one argument channel of BIGINT or INTEGER, read per row: a NULL argument gives a NULL output;
+ *     buckets <= 0 makes the first pa_op_get_output after finish fail with PA_ERR_INVALID_ARGUMENT ("Buckets must be greater than 0")
+ *     and nothing is emitted; otherwise N < buckets -> bucket = i, else with r = N % buckets, q = N / buckets:
+ *     bucket = i < (q + 1) * r ? i / (q + 1) : (i - r) / q, in int64.
+ *   Output, only after finish: the rows in sorted order; the input's output_channels as flat copies in descriptor order, then one
+ *     column per function in descriptor order (the same function may be asked for twice).  How the output is cut into pages is not part
+ *     of the contract.  An operator that received no rows produces no page.
+ *   needs_input = not finishing; is_finished = finishing and every output page taken; add_input after finish is PA_ERR_ILLEGAL_STATE;
+ *     empty pages are accepted.  The result is a function of the input row sequence alone: not of page boundaries, of host or device
+ *     input pages or their encodings, or of the run.
+ *   At creation, before any device work: PA_ERR_NOT_SUPPORTED for pre_grouped_channel_count != 0 or pre_sorted_channel_prefix != 0, a
+ *     partition or sort channel type pa_order_by_desc refuses as a sort channel (PA_LONG_DECIMAL, PA_ROW), PA_ROW output channels, more
+ *     than 8 partition channels; PA_ERR_INVALID_ARGUMENT for an unknown function id, a wrong argument_count, an argument channel out of
+ *     range, an ntile argument that is not BIGINT / INTEGER, function_count outside 1 .. 16, bad channel indices or sort orders.
+ *   More than INT32_MAX rows held, or the pool limit reached: PA_ERR_INSUFFICIENT_RESOURCES.  pa_op_memory_bytes reports the rows held
+ *     (+ scratch while allocated). */
+typedef enum pa_window_function {
+    PA_WINDOW_ROW_NUMBER = 0, PA_WINDOW_RANK = 1, PA_WINDOW_DENSE_RANK = 2, PA_WINDOW_PERCENT_RANK = 3, PA_WINDOW_CUME_DIST = 4, PA_WINDOW_NTILE = 5
+} pa_window_function;
+typedef struct pa_window_function_desc {
+    int32_t function;                    /* pa_window_function */
+    int32_t argument_count;              /* 0; ntile: 1 */
+    const int32_t* argument_channels;    /* may be NULL when there are none */
+} pa_window_function_desc;
+typedef struct pa_window_desc {          /* WindowOperatorFactory(sourceTypes, outputChannels, windowFunctionDefinitions, partitionChannels,
+                                          * preGroupedChannels, sortChannels, sortOrder, preSortedChannelPrefix, expectedPositions) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere; NULL = all 0 */
+    int32_t output_channel_count;
+    const int32_t* output_channels;
+    int32_t function_count;              /* 1 .. 16 */
+    const pa_window_function_desc* functions;
+    int32_t partition_channel_count;     /* 0 .. 8 */
+    const int32_t* partition_channels;   /* may be NULL when there are none */
+    int32_t sort_channel_count;          /* >= 0 */
+    const int32_t* sort_channels;        /* may be NULL when there are none */
+    const int32_t* sort_orders;          /* pa_sort_order per sort channel */
+    int32_t pre_grouped_channel_count;   /* must be 0 */
+    int32_t pre_sorted_channel_prefix;   /* must be 0 */
+    int32_t expected_positions;          /* >= 0; a hint, not read */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_window_desc;
+
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
  * factories in one Driver).  Semantically the composition of the three descriptors: the join's probe page is the projection
@@ -783,6 +853,8 @@ int32_t pa_topn_ranking_create(const pa_topn_ranking_desc* desc, pa_operator** o
  * pages in flight), *capacity = slots of the table (0 without), *rows_held = the rows the operator keeps right now, retained by the last
  * prune + not yet pruned (what getEstimatedSizeInBytes watches).  Any out pointer may be NULL. */
 int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity, int64_t* rows_held);
+/* Window (pa_window_desc above). */
+int32_t pa_window_create(const pa_window_desc* desc, pa_operator** out);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

@@ -588,6 +588,60 @@ inline TopNRankingStats topNRankingStats(Operator& op)
     return st;
 }
 
+// WindowOperatorFactory(sourceTypes, outputChannels, windowFunctionDefinitions, partitionChannels, preGroupedChannels, sortChannels,
+// sortOrder, preSortedChannelPrefix, expectedPositions) for the ranking functions: after finish, every row, sorted by the partition
+// channels (ASC_NULLS_LAST) then the sort channels, as the output channels with one column per window function behind them
+struct WindowFunctionDefinition {
+    int32_t function = PA_WINDOW_ROW_NUMBER;   // pa_window_function
+    std::vector<int32_t> argumentChannels;     // ntile: its bucket count channel
+};
+struct WindowOperatorFactory {
+    std::vector<int32_t> sourceTypes, outputChannels;
+    std::vector<WindowFunctionDefinition> functions;
+    std::vector<int32_t> partitionChannels, sortChannels, sortOrders;
+    int32_t preGroupedChannelCount = 0, preSortedChannelPrefix = 0, expectedPositions = 0, outputMem = PA_MEM_HOST;
+    std::vector<int32_t> typeParams;
+
+    WindowOperatorFactory(std::vector<int32_t> sourceTypes, std::vector<int32_t> outputChannels, std::vector<WindowFunctionDefinition> functions,
+                          std::vector<int32_t> partitionChannels, std::vector<int32_t> sortChannels, std::vector<int32_t> sortOrders,
+                          int32_t expectedPositions = 0, int32_t outputMem = PA_MEM_HOST)
+        : sourceTypes(std::move(sourceTypes)), outputChannels(std::move(outputChannels)), functions(std::move(functions)),
+          partitionChannels(std::move(partitionChannels)), sortChannels(std::move(sortChannels)), sortOrders(std::move(sortOrders)),
+          expectedPositions(expectedPositions), outputMem(outputMem)
+    {
+    }
+
+    std::unique_ptr<Operator> createOperator() const
+    {
+        std::vector<pa_window_function_desc> fs(functions.size());
+        for (size_t i = 0; i < functions.size(); i++) {
+            fs[i].function = functions[i].function;
+            fs[i].argument_count = (int32_t)functions[i].argumentChannels.size();
+            fs[i].argument_channels = functions[i].argumentChannels.data();
+        }
+        pa_window_desc d{};
+        d.input_channel_count = (int32_t)sourceTypes.size();
+        d.input_types = sourceTypes.data();
+        d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        d.output_channel_count = (int32_t)outputChannels.size();
+        d.output_channels = outputChannels.data();
+        d.function_count = (int32_t)fs.size();
+        d.functions = fs.data();
+        d.partition_channel_count = (int32_t)partitionChannels.size();
+        d.partition_channels = partitionChannels.data();
+        d.sort_channel_count = (int32_t)sortChannels.size();
+        d.sort_channels = sortChannels.data();
+        d.sort_orders = sortOrders.data();
+        d.pre_grouped_channel_count = preGroupedChannelCount;
+        d.pre_sorted_channel_prefix = preSortedChannelPrefix;
+        d.expected_positions = expectedPositions;
+        d.output_mem = outputMem;
+        pa_operator* h = nullptr;
+        check(pa_window_create(&d, &h));
+        return std::make_unique<Operator>(h);
+    }
+};
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

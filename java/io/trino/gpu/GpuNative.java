@@ -90,6 +90,12 @@ final class GpuNative
             int[] sortChannels, int[] sortOrders, int maxRowCountPerPartition, boolean partial, int hashChannel, int expectedPositions, int outputMem);
     /** {partitions seen so far, slots of the table, rows held right now} of a TopNRanking operator (what getEstimatedSizeInBytes watches). */
     static native long[] topNRankingStats(long operator);
+    /** WindowOperatorFactory(sourceTypes, outputChannels, windowFunctionDefinitions, partitionChannels, preGroupedChannels, sortChannels,
+     *  sortOrder, preSortedChannelPrefix, expectedPositions) for the ranking functions: functions = pa_window_function ids,
+     *  functionArguments = one argument channel per function, -1 where it takes none (GpuWindow). */
+    static native long createWindow(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] functions, int[] functionArguments,
+            int[] partitionChannels, int[] sortChannels, int[] sortOrders, int preGroupedChannelCount, int preSortedChannelPrefix,
+            int expectedPositions, int outputMem);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

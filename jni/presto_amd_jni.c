@@ -662,6 +662,40 @@ JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_topNRankingStats(JNIEnv
     return out;
 }
 
+/* LocalExecutionPlanner.visitWindow: WindowOperatorFactory for the ranking functions (GpuWindow).  functions = pa_window_function per
+ * window function, functionArguments = one argument channel per function, -1 where it takes none (only ntile takes one);
+ * sortOrders = SortOrder ordinals; typeParams as above. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createWindow(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams, jintArray outputChannels,
+        jintArray functions, jintArray functionArguments, jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders,
+        jint preGroupedChannelCount, jint preSortedChannelPrefix, jint expectedPositions, jint outputMem)
+{
+    jsize n, no, nf, nfa, npc, nsc, nso, np_ = 0, i;
+    pa_window_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *oc = ints_of(env, outputChannels, &no), *fn = ints_of(env, functions, &nf);
+    int32_t *fa = ints_of(env, functionArguments, &nfa), *pc = ints_of(env, partitionChannels, &npc);
+    int32_t *sc = ints_of(env, sortChannels, &nsc), *so = ints_of(env, sortOrders, &nso);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    if (nf != nfa) nf = 0;   /* (refused below: function_count 0) */
+    pa_window_function_desc* fs = (pa_window_function_desc*)calloc((size_t)(nf > 0 ? nf : 1), sizeof *fs);
+    for (i = 0; fs && fn && fa && i < nf; i++) {
+        fs[i].function = fn[i];
+        fs[i].argument_count = fa[i] >= 0 ? 1 : 0;
+        fs[i].argument_channels = fa + i;
+    }
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.output_channel_count = no; d.output_channels = oc; d.function_count = fs ? nf : 0; d.functions = fs;
+    d.partition_channel_count = npc; d.partition_channels = pc;
+    d.sort_channel_count = nsc == nso ? nsc : -1; d.sort_channels = sc; d.sort_orders = so;
+    d.pre_grouped_channel_count = preGroupedChannelCount; d.pre_sorted_channel_prefix = preSortedChannelPrefix;
+    d.expected_positions = expectedPositions; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_window_create(&d, &op);
+    free(fs); free(params); free(so); free(sc); free(pc); free(fa); free(fn); free(oc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

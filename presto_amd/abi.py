@@ -395,6 +395,39 @@ class pa_topn_ranking_desc(C.Structure):
     ]
 
 
+WINDOW_ROW_NUMBER, WINDOW_RANK, WINDOW_DENSE_RANK, WINDOW_PERCENT_RANK, WINDOW_CUME_DIST, WINDOW_NTILE = 0, 1, 2, 3, 4, 5   # pa_window_function
+
+
+class pa_window_function_desc(C.Structure):
+    _fields_ = [
+        ("function", C.c_int32),
+        ("argument_count", C.c_int32),
+        ("argument_channels", C.POINTER(C.c_int32)),
+    ]
+
+
+class pa_window_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("output_channel_count", C.c_int32),
+        ("output_channels", C.POINTER(C.c_int32)),
+        ("function_count", C.c_int32),
+        ("functions", C.POINTER(pa_window_function_desc)),
+        ("partition_channel_count", C.c_int32),
+        ("partition_channels", C.POINTER(C.c_int32)),
+        ("sort_channel_count", C.c_int32),
+        ("sort_channels", C.POINTER(C.c_int32)),
+        ("sort_orders", C.POINTER(C.c_int32)),
+        ("pre_grouped_channel_count", C.c_int32),
+        ("pre_sorted_channel_prefix", C.c_int32),
+        ("expected_positions", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

@@ -677,6 +677,16 @@ int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* cap
     });
 }
 
+// ---- Window ----
+int32_t pa_window_create(const pa_window_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_window(desc);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

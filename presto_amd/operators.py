@@ -941,6 +941,58 @@ def TopNRankingOperator(input_types, output_channels, partition_channels, sort_c
                                       hash_channel, expected_positions, output_mem, stream, type_params).createOperator()
 
 
+# ---- WINDOW ------------------------------------------------------------------------------------------------
+def WindowOperatorFactory(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count=0,
+                          pre_sorted_channel_prefix=0, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """WindowOperatorFactory(sourceTypes, outputChannels, windowFunctionDefinitions, partitionChannels, preGroupedChannels, sortChannels,
+    sortOrder, preSortedChannelPrefix, expectedPositions) (…/operator/WindowOperator.java) for the ranking functions: after finish, every
+    row, sorted by partition channels (ASC_NULLS_LAST) then sort channels (ties in arrival order), as the output channels with one column
+    per function behind them.  functions: abi.WINDOW_* ids, or (id, [argument channels]) -- ntile takes its bucket count channel."""
+    d = abi.pa_window_desc()
+    types = abi.int32_array(input_types)
+    oc = abi.int32_array(output_channels)
+    pc = abi.int32_array(partition_channels)
+    sc = abi.int32_array(sort_channels)
+    so = abi.int32_array(sort_orders)
+    functions = [(f, []) if isinstance(f, int) else f for f in functions]
+    fs = (abi.pa_window_function_desc * max(len(functions), 1))()
+    keep = [types, oc, pc, sc, so, fs]
+    for i, (function, arguments) in enumerate(functions):
+        args = abi.int32_array(arguments)
+        keep.append(args)
+        fs[i].function = function
+        fs[i].argument_count = len(arguments)
+        fs[i].argument_channels = C.cast(args, C.POINTER(C.c_int32))
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.output_channel_count = len(output_channels)
+    d.output_channels = C.cast(oc, C.POINTER(C.c_int32))
+    d.function_count = len(functions)
+    d.functions = C.cast(fs, C.POINTER(abi.pa_window_function_desc))
+    d.partition_channel_count = len(partition_channels)
+    d.partition_channels = C.cast(pc, C.POINTER(C.c_int32))
+    d.sort_channel_count = len(sort_channels)
+    d.sort_channels = C.cast(sc, C.POINTER(C.c_int32))
+    d.sort_orders = C.cast(so, C.POINTER(C.c_int32))
+    d.pre_grouped_channel_count = pre_grouped_channel_count
+    d.pre_sorted_channel_prefix = pre_sorted_channel_prefix
+    d.expected_positions = expected_positions
+    d.output_mem = output_mem
+    d.stream = stream
+    return OperatorFactory(lib().pa_window_create, d, keep)
+
+
+def WindowOperator(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count=0,
+                   pre_sorted_channel_prefix=0, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    return WindowOperatorFactory(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count,
+                                 pre_sorted_channel_prefix, expected_positions, output_mem, stream, type_params).createOperator()
+
+
 # ---- driver loop ---------------------------------------------------------------------------------------
 def to_pages(operator, input_pages):
     """OperatorAssertion.toPages (core/trino-main/src/test/java/io/trino/operator/OperatorAssertion.java:62-138):
