@@ -10,9 +10,11 @@
 // last sort channel to the first, each image by one stable sort of (image, row id) pairs over the bits in which the images
 // differ (sort_kernels.hip), the NULL digit by the stable partition the exchange already uses.  Fully tied rows keep arrival
 // order.  A first sort channel of integers without NULL rows that is also an output channel is written from the sorted images.
+// The rows are collected in, and the output channels gathered out of, a HeldRows (held_rows.hpp).
 #include <algorithm>
 #include <cstring>
 
+#include "held_rows.hpp"
 #include "keyed_operator.hpp"
 #include "operator.hpp"
 #include "scan_kernels.hpp"
@@ -22,21 +24,7 @@
 
 namespace pa {
 
-void launch_sort_null_digits(const uint8_t* nulls, const int32_t* perm, int64_t n, int nulls_first, int32_t* digits, hipStream_t s);
-void launch_varchar_chunk_keys(const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int chunk, int descending,
-                               uint64_t* keys, hipStream_t s);
-void launch_iota_i32(int32_t* dst, int64_t n, hipStream_t s);
-int32_t varchar_max_length(const int32_t* offsets, int64_t n, void* temp_dev_8, hipStream_t s);
-
 namespace {
-
-// all rows of the input so far, column by column (PagesIndex.addPage; flat device arrays: address == position)
-struct Accumulated {
-    int32_t type = PA_BIGINT;
-    bool varwidth = false, has_nulls = false;
-    DevBuf values, offsets, nulls;
-    int64_t bytes = 0;  // VARCHAR bytes used
-};
 
 class OrderByOperator : public pa_operator {
 public:
@@ -59,14 +47,10 @@ public:
         for (int c : sort_channels_) check_key_type(types_[(size_t)c], "sort");
         for (int c : output_channels_) check_carried_type(types_[(size_t)c], "output");
         output_mem_ = d->output_mem;
-        cols_.resize(types_.size());
         needed_.assign(types_.size(), false);
         for (int c : output_channels_) needed_[(size_t)c] = true;
         for (int c : sort_channels_) needed_[(size_t)c] = true;
-        for (size_t c = 0; c < types_.size(); c++) {
-            cols_[c].type = types_[c];
-            cols_[c].varwidth = types_[c] == PA_VARCHAR;
-        }
+        store_.init(types_, needed_);
     }
     ~OrderByOperator() override
     {
@@ -96,7 +80,7 @@ public:
             return;
         }
         const int64_t m = page->position_count;
-        if (rows_ + m > INT32_MAX) {
+        if (store_.rows + m > INT32_MAX) {
             if (retained) page->release(page->release_ctx);   // (nothing of it was read)
             throw Error(PA_ERR_INSUFFICIENT_RESOURCES, "too many rows for one sort");
         }
@@ -109,7 +93,7 @@ public:
                 h.release_ctx = page->release_ctx;
             }
             held_.push_back(std::move(h));
-            rows_ += m;
+            store_.rows += m;
             return;
         }
         // (a retained page that is copied goes back to its owner when the copies have run -- also when a check below throws)
@@ -127,7 +111,7 @@ public:
         flush_held();
         hipStream_t s = stream_.get();
         DevPage dp = stager_.stage(page, &needed_, s);
-        append(dp);
+        store_.append_page(dp, dp.n, s);
         PA_HIP(hipStreamSynchronize(s));  // the stager's buffers are reused by the next page
     }
 
@@ -146,10 +130,7 @@ public:
     {
         if (held_.empty()) return;
         hipStream_t s = stream_.get();
-        const int64_t total = rows_;
-        int64_t listed = 0;
-        for (const Held& h : held_) listed += h.rows;
-        rows_ = total - listed;   // (append counts them again)
+        for (const Held& h : held_) store_.rows -= h.rows;   // (append_page counts them again)
         std::vector<Held> held;
         held.swap(held_);
         struct ReleaseAll {
@@ -173,46 +154,8 @@ public:
                 dp.cols[c].values = h.cols[c].values;
                 dp.cols[c].nulls = h.cols[c].nulls;
             }
-            append(dp);
+            store_.append_page(dp, dp.n, s);
         }
-    }
-
-    void append(const DevPage& dp)
-    {
-        hipStream_t s = stream_.get();
-        const int64_t m = dp.n;
-        for (size_t c = 0; c < types_.size(); c++) {
-            if (!needed_[c]) continue;
-            const DevColumn& in = dp.cols[c];
-            PA_REQUIRE(in.type == types_[c], PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared input type");
-            Accumulated& a = cols_[c];
-            if (a.varwidth) {
-                int32_t ends[2];
-                PA_HIP(hipMemcpyAsync(&ends[0], in.offsets, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipMemcpyAsync(&ends[1], in.offsets + m, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                const int64_t add = ends[1] - ends[0];
-                PA_REQUIRE(a.bytes + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "VARCHAR column exceeds 2 GB");
-                int32_t* off = static_cast<int32_t*>(a.offsets.reserve_keep((size_t)(rows_ + m + 1) * 4, (size_t)(rows_ ? rows_ + 1 : 0) * 4, s));
-                launch_offsets_append(in.offsets, m, (int32_t)a.bytes, off + rows_, rows_ == 0, s);
-                char* v = static_cast<char*>(a.values.reserve_keep((size_t)(a.bytes + add + 1), (size_t)a.bytes, s));
-                if (add) PA_HIP(hipMemcpyAsync(v + a.bytes, static_cast<const char*>(in.values) + ends[0], (size_t)add, hipMemcpyDeviceToDevice, s));
-                a.bytes += add;
-            }
-            else {
-                const size_t w = (size_t)type_width(a.type);
-                char* v = static_cast<char*>(a.values.reserve_keep((size_t)(rows_ + m) * w, (size_t)rows_ * w, s));
-                PA_HIP(hipMemcpyAsync(v + (size_t)rows_ * w, in.values, (size_t)m * w, hipMemcpyDeviceToDevice, s));
-            }
-            if (in.nulls || a.has_nulls) {
-                uint8_t* nl = static_cast<uint8_t*>(a.nulls.reserve_keep((size_t)(rows_ + m), a.has_nulls ? (size_t)rows_ : 0, s));
-                if (!a.has_nulls && rows_ > 0) PA_HIP(hipMemsetAsync(nl, 0, (size_t)rows_, s));
-                if (in.nulls) PA_HIP(hipMemcpyAsync(nl + rows_, in.nulls, (size_t)m, hipMemcpyDeviceToDevice, s));
-                else PA_HIP(hipMemsetAsync(nl + rows_, 0, (size_t)m, s));
-                a.has_nulls = true;
-            }
-        }
-        rows_ += m;
     }
 
     void finish() override { finishing_ = true; }
@@ -222,22 +165,22 @@ public:
     {
         if (!finishing_ || output_done_) return false;
         output_done_ = true;
-        if (rows_ == 0) return false;
+        if (store_.rows == 0) return false;
         hipStream_t s = stream_.get();
-        if (held_.size() == 1 && held_[0].rows == rows_) {
+        if (held_.size() == 1 && held_[0].rows == store_.rows) {
             // the one page of the input, still where its owner put it: its block arrays ARE the columns (released when the operator goes)
             for (size_t c = 0; c < types_.size(); c++) {
                 if (!needed_[c]) continue;
                 const pa_column& in = held_[0].cols[c];
-                cols_[c].values.borrow(in.values, (size_t)rows_ * type_width(types_[c]));
+                store_.cols[c].values.borrow(in.values, (size_t)store_.rows * type_width(types_[c]));
                 if (in.nulls) {
-                    cols_[c].nulls.borrow(in.nulls, (size_t)rows_);
-                    cols_[c].has_nulls = true;
+                    store_.cols[c].nulls.borrow(in.nulls, (size_t)store_.rows);
+                    store_.cols[c].has_nulls = true;
                 }
             }
         }
         else flush_held();
-        const int64_t n = rows_;
+        const int64_t n = store_.rows;
         int32_t* perm = static_cast<int32_t*>(perm_[0].ensure((size_t)n * 4));
         int32_t* next = static_cast<int32_t*>(perm_[1].ensure((size_t)n * 4));
         int32_t* digits = static_cast<int32_t*>(digits_.ensure((size_t)n * 4));
@@ -275,11 +218,11 @@ public:
         SortPayload payload;
         memset(&payload, 0, sizeof payload);
         {
-            const Accumulated& f = cols_[(size_t)sort_channels_[0]];
+            const OutColumn& f = store_.cols[(size_t)sort_channels_[0]];
             const bool images_serve = !f.varwidth && !f.has_nulls && (f.type == PA_BIGINT || f.type == PA_INTEGER || f.type == PA_DATE);
             if (!f.varwidth && !f.has_nulls && !getenv("PRESTO_AMD_SORT_NO_PAYLOAD")) {
                 for (size_t j = 0; j < outs.size() && payload.count < PA_SORT_MAX_PAYLOAD; j++) {
-                    const Accumulated& a = cols_[(size_t)outs[j]];
+                    const OutColumn& a = store_.cols[(size_t)outs[j]];
                     const int w = a.varwidth ? 0 : type_width(a.type);
                     if (a.has_nulls || (w != 4 && w != 8)) continue;
                     if (outs[j] == sort_channels_[0] && images_serve) continue;   // (written from the sorted images)
@@ -330,7 +273,7 @@ public:
             sorted_images = kp[1];
         };
         for (int i = (int)sort_channels_.size() - 1; i >= 0; i--) {
-            const Accumulated& a = cols_[(size_t)sort_channels_[i]];
+            const OutColumn& a = store_.cols[(size_t)sort_channels_[i]];
             const int order = sort_orders_[i];
             const bool descending = order >= 2, nulls_first = (order & 1) == 0;
             const uint8_t* nulls = a.has_nulls ? a.nulls.as<uint8_t>() : nullptr;
@@ -358,76 +301,33 @@ public:
         }
         materialize();   // (no sort ran: every image the same)
         timer.end(s);
-        // the first sort channel as an output channel: its sorted images ARE the column (integers without NULL rows), no gather
+        // Output channels in sorted order (PagesIndex.appendTo).  Two kinds of channel are not gathered: one the sort brought along, and
+        // the first sort channel as an output channel, whose sorted images ARE the column (integers without NULL rows).
         const int first_channel = sort_channels_[0];
-        const bool first_descending = sort_orders_[0] >= 2;
         {
-            const Accumulated& f = cols_[(size_t)first_channel];
+            const OutColumn& f = store_.cols[(size_t)first_channel];
             if (f.varwidth || f.has_nulls || !(f.type == PA_BIGINT || f.type == PA_INTEGER || f.type == PA_DATE)) sorted_images = nullptr;
         }
-        // output channels in sorted order (PagesIndex.appendTo)
         out_cols_.clear();
         out_cols_.resize(outs.size());
-        // the fixed-width channels (and every NULL flag array) are gathered through the permutation by ONE launch: the permutation is
-        // read once, the random reads of all channels are in flight together
-        GatherMultiArgs gm;
-        memset(&gm, 0, sizeof gm);
-        gm.positions[0] = perm;
-        gm.count = n;
-        auto flush_gather = [&] {
-            if (gm.ncols > 0) launch_gather_multi(gm, s);
-            gm.ncols = 0;
-        };
+        std::vector<bool> produced(outs.size(), false);
         for (size_t j = 0; j < outs.size(); j++) {
-            const Accumulated& a = cols_[(size_t)outs[j]];
-            OutColumn& oc = out_cols_[j];
-            oc.type = a.type;
-            oc.varwidth = a.varwidth;
-            const uint8_t* nulls = a.has_nulls ? a.nulls.as<uint8_t>() : nullptr;
-            oc.has_nulls = nulls != nullptr;
-            if (gm.ncols == GATHER_MULTI_MAX_COLS) flush_gather();
-            GatherMultiCol& gc = gm.col[gm.ncols];
-            memset(&gc, 0, sizeof gc);
-            gc.width = 1;
-            if (a.varwidth) {
-                int32_t* lens = static_cast<int32_t*>(oc.offsets.ensure((size_t)(n + 1) * 4));
-                int32_t* total = reinterpret_cast<int32_t*>(counts);
-                launch_varwidth_lengths(perm, n, a.offsets.as<int32_t>(), nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, n, total, scan_temp_.ensure(scan_temp_bytes(n)), s);
-                int32_t h_total = 0;
-                PA_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                launch_varwidth_copy(perm, n, a.offsets.as<int32_t>(), a.values.as<uint8_t>(), nulls, lens,
-                                     static_cast<uint8_t*>(oc.values.ensure((size_t)(h_total > 0 ? h_total : 1))), total, s);
-            }
-            else if (payload_moved && payload_of[j] >= 0) {
-                oc.values = std::move(payload_out_[payload_of[j]]);   // the sort brought the channel along
-            }
-            else if (sorted_images != nullptr && outs[j] == first_channel) {
-                launch_topn_values_of_keys(a.type, sorted_images, n, first_descending, oc.values.ensure((size_t)n * type_width(a.type)), s);
-            }
-            else {
-                const int w = type_width(a.type);   // (1, 4, 8, or 16 for a LONG_DECIMAL: the constructor refused every other type)
-                gc.src = a.values.ptr();
-                gc.dst = oc.values.ensure((size_t)n * w);
-                gc.width = w;
-            }
-            if (nulls) {
-                gc.src_nulls = nulls;
-                gc.dst_nulls = static_cast<uint8_t*>(oc.nulls.ensure((size_t)n));
-            }
-            if (gc.dst || gc.dst_nulls) gm.ncols++;
+            const OutColumn& a = store_.cols[(size_t)outs[j]];
+            if (a.varwidth) continue;
+            if (payload_moved && payload_of[j] >= 0) out_cols_[j].values = std::move(payload_out_[payload_of[j]]);
+            else if (sorted_images != nullptr && outs[j] == first_channel)
+                launch_topn_values_of_keys(a.type, sorted_images, n, sort_orders_[0] >= 2, out_cols_[j].values.ensure((size_t)n * type_width(a.type)), s);
+            else continue;
+            produced[j] = true;
         }
-        flush_gather();
+        store_.gather_sorted(perm, n, outs, &produced, out_cols_, scan_temp_, reinterpret_cast<int32_t*>(counts), s);
         publish_output(out_cols_, (int32_t)n, output_mem_, s, out, out_storage_);
         return true;
     }
 
     int64_t memory_bytes() override
     {
-        int64_t b = 0;
-        for (const auto& a : cols_) b += (int64_t)(a.values.capacity() + a.offsets.capacity() + a.nulls.capacity());
-        return b;
+        return (int64_t)store_.bytes();
     }
 
 private:
@@ -436,7 +336,7 @@ private:
     std::vector<int32_t> types_, sort_orders_;
     std::vector<int> output_channels_, sort_channels_;
     std::vector<bool> needed_;
-    std::vector<Accumulated> cols_;
+    HeldRows store_;   // (store_.rows counts the rows of the listed pages too)
     // device pages listed instead of copied (add_input)
     struct Held {
         int64_t rows = 0;
@@ -445,7 +345,6 @@ private:
         void* release_ctx = nullptr;
     };
     std::vector<Held> held_;
-    int64_t rows_ = 0;
     int32_t output_mem_ = PA_MEM_HOST;
     bool finishing_ = false, output_done_ = false;
     DevBuf payload_out_[PA_SORT_MAX_PAYLOAD];

@@ -11,8 +11,8 @@
 // reference finds peers with IS NOT DISTINCT FROM but orders with Double.compare, so its own result for such a partition depends on
 // arrival order).
 //
-// State is bounded by what can still matter.  The operator holds rows, column by column, as [rows retained by the last prune | rows
-// appended since]:
+// State is bounded by what can still matter.  The operator holds rows in a HeldRows (held_rows.hpp) as [rows retained by the last
+// prune | rows appended since]:
 //   per page   group ids (DistinctHash::add_page), the image of the first sort channel (launch_topn_keys), the arrival filter
 //              keep = image <= bound[gid] (topn_ranking_kernels.hpp), keep counts -> scan -> positions (KeepCompactor,
 //              keyed_operator.hpp), Block.copyPositions of the survivors behind the held rows;
@@ -24,6 +24,7 @@
 // dropped under a tighter one.  A prune itself drops only rows that n others strictly precede (ROW_NUMBER: in (order, arrival)).
 #include <cstdlib>
 
+#include "held_rows.hpp"
 #include "keyed_operator.hpp"
 #include "row_sort.hpp"
 #include "topn_ranking_kernels.hpp"
@@ -87,17 +88,6 @@ void* checked_stream(const pa_topn_ranking_desc* d)
     return d->stream;
 }
 
-DevColumn view_of(const OutColumn& o)
-{
-    DevColumn c;
-    c.type = o.type;
-    c.varwidth = o.varwidth;
-    c.values = o.values.ptr();
-    c.offsets = o.offsets.as<int32_t>();
-    c.nulls = o.has_nulls ? o.nulls.as<uint8_t>() : nullptr;
-    return c;
-}
-
 class TopNRankingOperator : public pa_operator {
 public:
     explicit TopNRankingOperator(const pa_topn_ranking_desc* d)
@@ -114,12 +104,7 @@ public:
         for (int32_t c : partition_channels_) needed_[c] = true;
         for (int32_t c : sort_channels_) needed_[c] = kept_channel_[c] = true;
         for (int32_t c : output_channels_) needed_[c] = kept_channel_[c] = true;
-        held_.resize(types_.size());
-        held_bytes_.assign(types_.size(), 0);
-        for (size_t c = 0; c < types_.size(); c++) {
-            held_[c].type = types_[c];
-            held_[c].varwidth = types_[c] == PA_VARCHAR;
-        }
+        held_.init(types_, kept_channel_);
         // (read per operator, so that a test can change it between operators of one process)
         if (const char* e = getenv("PRESTO_AMD_TOPN_RANKING_PRUNE_ROWS")) {
             const long long v = atoll(e);
@@ -138,11 +123,11 @@ public:
     {
         if (partitions) *partitions = hash_ ? hash_->settle(stream_.get()) : 1;
         if (capacity) *capacity = hash_ ? hash_->capacity() : 0;
-        if (rows_held) *rows_held = rows_;
+        if (rows_held) *rows_held = held_.rows;
     }
 
     bool needs_input() override { return !finishing_; }
-    bool is_finished() override { return finishing_ && (done_ || rows_ == 0); }
+    bool is_finished() override { return finishing_ && (done_ || held_.rows == 0); }
     void finish() override { finishing_ = true; }
 
     void add_input(const pa_page* page) override
@@ -179,8 +164,8 @@ public:
             int32_t kept = 0;
             const int32_t* positions = kept_rows_.positions_of(keep, m, &kept, "topn ranking", s);
             if (kept > 0) {
-                if (rows_ + kept > INT32_MAX) prune(s);
-                PA_REQUIRE(rows_ + kept <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "more rows held than one sort takes");
+                if (held_.rows + kept > INT32_MAX) prune(s);
+                PA_REQUIRE(held_.rows + kept <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "more rows held than one sort takes");
                 append(slice_of(in, at), gids + at, positions, kept, s);
             }
             if (appended_ >= std::max(threshold_, retained_)) prune(s);
@@ -193,20 +178,20 @@ public:
     {
         if (!finishing_ || done_) return false;
         done_ = true;
-        if (rows_ == 0) return false;
+        if (held_.rows == 0) return false;
         hipStream_t s = stream_.get();
         // a prune leaves the held rows in output order and their ranking in ranking_kept_: nothing to do when none arrived since the last
         if (appended_ > 0) prune(s);
         const size_t nc = output_channels_.size();
         out_cols_.clear();
         out_cols_.resize(nc + (partial_ ? 0 : 1));
-        for (size_t c = 0; c < nc; c++) view_column(out_cols_[c], view_of(held_[output_channels_[c]]));
+        for (size_t c = 0; c < nc; c++) view_column(out_cols_[c], held_.view(output_channels_[c]));
         if (!partial_) {
             DevColumn ranking;   // BIGINT, flat, no nulls
             ranking.values = ranking_kept_.ptr();
             view_column(out_cols_[nc], ranking);
         }
-        publish_output(out_cols_, (int32_t)rows_, output_mem_, s, out, storage_);
+        publish_output(out_cols_, (int32_t)held_.rows, output_mem_, s, out, storage_);
         return true;
     }
 
@@ -217,8 +202,7 @@ public:
     {
         size_t b = stager_.bytes() + gids_.capacity() + images_.capacity() + mark_.capacity() + keep_.capacity() + kept_rows_.bytes() + gather_.bytes() + held_gids_.capacity() + bound_.capacity() + run_start_.capacity() +
                    ranking_kept_.capacity() + sorter_.bytes() + varchar_tmp_.values.capacity() + varchar_tmp_.offsets.capacity() + varchar_tmp_.nulls.capacity();
-        for (const OutColumn& o : held_) b += o.values.capacity() + o.offsets.capacity() + o.nulls.capacity();
-        return (hash_ ? hash_->memory_bytes() : 0) + (int64_t)b;
+        return (hash_ ? hash_->memory_bytes() : 0) + (int64_t)(b + held_.bytes());
     }
 
 private:
@@ -243,50 +227,22 @@ private:
     // Block.copyPositions of the page's survivors behind the held rows, with their group ids
     void append(const DevPage& in, const uint64_t* gids, const int32_t* positions, int32_t k, hipStream_t s)
     {
-        const int64_t rows = rows_;
-        for (size_t c = 0; c < types_.size(); c++) {
-            if (!kept_channel_[c]) continue;
-            const DevColumn& src = in.cols[c];
-            OutColumn& h = held_[c];
-            if (h.varwidth) {
-                gather_.copy_positions(src, positions, k, varchar_tmp_, s);   // offsets from 0, k + 1 of them
-                int32_t add = 0;
-                read_back(&add, varchar_tmp_.offsets.as<int32_t>() + k, 4, s);
-                PA_REQUIRE(add >= 0 && held_bytes_[c] + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "VARCHAR column exceeds 2 GB");
-                int32_t* off = static_cast<int32_t*>(h.offsets.reserve_keep((size_t)(rows + k + 1) * 4, (size_t)(rows ? rows + 1 : 0) * 4, s));
-                launch_offsets_append(varchar_tmp_.offsets.as<int32_t>(), k, (int32_t)held_bytes_[c], off + rows, rows == 0, s);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(held_bytes_[c] + add + 1), (size_t)held_bytes_[c], s));
-                if (add) PA_HIP(hipMemcpyAsync(v + held_bytes_[c], varchar_tmp_.values.ptr(), (size_t)add, hipMemcpyDeviceToDevice, s));
-                held_bytes_[c] += add;
-            }
-            else {
-                const size_t w = (size_t)type_width(h.type);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(rows + k) * w, (size_t)rows * w, s));
-                launch_gather_flat(src.values, (int)w, positions, k, v + (size_t)rows * w, s);
-            }
-            if (src.nulls || h.has_nulls) {
-                uint8_t* nl = static_cast<uint8_t*>(h.nulls.reserve_keep((size_t)(rows + k), h.has_nulls ? (size_t)rows : 0, s));
-                if (!h.has_nulls && rows > 0) PA_HIP(hipMemsetAsync(nl, 0, (size_t)rows, s));
-                if (src.nulls) launch_gather_nulls(src.nulls, positions, k, nl + rows, s);
-                else PA_HIP(hipMemsetAsync(nl + rows, 0, (size_t)k, s));
-                h.has_nulls = true;
-            }
-        }
+        const int64_t rows = held_.rows;
+        held_.append_positions(in, positions, k, gather_, varchar_tmp_, s);
         uint64_t* hg = static_cast<uint64_t*>(held_gids_.reserve_keep((size_t)(rows + k) * 8, (size_t)rows * 8, s));
         launch_gather_flat(gids, 8, positions, k, hg + rows, s);
-        rows_ += k;
         appended_ += k;
     }
 
     // sort the held rows by (gid, sort channels), number / rank them, keep what can still matter, rewrite the bounds
     void prune(hipStream_t s)
     {
-        const int64_t n = rows_;
+        const int64_t n = held_.rows;
         if (n == 0) return;
         const int64_t partitions = hash_ ? hash_->settle(s) : 1;
         grow_bounds(partitions, s);
         std::vector<DevColumn> cols;
-        for (int32_t c : sort_channels_) cols.push_back(view_of(held_[c]));
+        for (int32_t c : sort_channels_) cols.push_back(held_.view(c));
         // The held array is [retained | appended]: the retained rows are in (gid, order, arrival) order and arrived before every
         // appended row, and appended rows stand in arrival order.  So array order is arrival order inside every class of rows that
         // compare equal, and the stable sort keeps it there: no sequence column is needed.
@@ -337,24 +293,14 @@ private:
         int32_t* rowids = static_cast<int32_t*>(rowids_buf.ensure((size_t)kept * 4));
         launch_gather_flat(perm, 4, sorted_positions, kept, rowids, s);
         // the rows kept into fresh columns, in output order
-        for (size_t c = 0; c < types_.size(); c++) {
-            if (!kept_channel_[c]) continue;
-            OutColumn fresh;
-            gather_.copy_positions(view_of(held_[c]), rowids, kept, fresh, s);
-            if (fresh.varwidth) {
-                int32_t bytes = 0;
-                read_back(&bytes, fresh.offsets.as<int32_t>() + kept, 4, s);
-                held_bytes_[c] = bytes;
-            }
-            held_[c] = std::move(fresh);   // (the old arrays go back to the pool tagged with this stream)
-        }
+        held_.keep_positions(rowids, kept, gather_, s);
         DevBuf fresh_gids;
         launch_gather_flat(sorted_gids, 8, sorted_positions, kept, fresh_gids.ensure((size_t)kept * 8), s);
         launch_gather_flat(a.ranking, 8, sorted_positions, kept, ranking_kept_.ensure((size_t)kept * 8), s);
         PA_HIP(hipStreamSynchronize(s));
         held_gids_ = std::move(fresh_gids);
         sorter_.release();
-        rows_ = retained_ = kept;
+        retained_ = kept;
         appended_ = 0;
     }
 
@@ -369,10 +315,9 @@ private:
     int64_t threshold_ = kDefaultPruneRows;
     int32_t output_mem_ = PA_MEM_HOST;
     // the rows held: [retained | appended], by input channel, with their group ids
-    std::vector<OutColumn> held_;
-    std::vector<int64_t> held_bytes_;   // VARCHAR bytes used
+    HeldRows held_;
     DevBuf held_gids_;
-    int64_t rows_ = 0, retained_ = 0, appended_ = 0;
+    int64_t retained_ = 0, appended_ = 0;
     DevBuf bound_, run_start_;
     int64_t bound_n_ = 0;
     DevBuf gids_, images_, mark_, keep_, ranking_kept_;

@@ -10,7 +10,7 @@
 // Contract (include/presto_amd.h).  Output only after finish: every input row, sorted by [partition channels ASC_NULLS_LAST] + [sort
 // channels], rows that compare equal in arrival order; the output channels, then one column per function.
 //
-// The operator holds every needed channel of the input, column by column, pages laid behind each other (as OrderBy does).  At the
+// The operator holds every needed channel of the input in a HeldRows (held_rows.hpp), as OrderBy does.  At the
 // first get_output after finish:
 //   sort       RowSorter (row_sort.hpp) over partition + sort channels: a permutation, stable, so arrival order inside ties;
 //   flags      one launch per channel: IS DISTINCT FROM the sorted row before (window_kernels.hpp) -> partition and peer flags;
@@ -21,6 +21,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "held_rows.hpp"
 #include "keyed_operator.hpp"
 #include "row_sort.hpp"
 #include "static_kernels.hpp"
@@ -72,17 +73,6 @@ void* checked_stream(const pa_window_desc* d)
     return d->stream;
 }
 
-DevColumn view_of(const OutColumn& o)
-{
-    DevColumn c;
-    c.type = o.type;
-    c.varwidth = o.varwidth;
-    c.values = o.values.ptr();
-    c.offsets = o.offsets.as<int32_t>();
-    c.nulls = o.has_nulls ? o.nulls.as<uint8_t>() : nullptr;
-    return c;
-}
-
 class WindowOperator : public pa_operator {
 public:
     explicit WindowOperator(const pa_window_desc* d) : stream_(checked_stream(d))
@@ -109,12 +99,7 @@ public:
         for (int32_t c : output_channels_) needed_[c] = true;
         for (int32_t c : argument_channels_)
             if (c >= 0) needed_[c] = true;
-        held_.resize(types_.size());
-        held_bytes_.assign(types_.size(), 0);
-        for (size_t c = 0; c < types_.size(); c++) {
-            held_[c].type = types_[c];
-            held_[c].varwidth = types_[c] == PA_VARCHAR;
-        }
+        held_.init(types_, needed_);
         timer.set_name("k_window_functions");
     }
     ~WindowOperator() override { (void)hipStreamSynchronize(stream_.get()); }
@@ -122,7 +107,7 @@ public:
     hipStream_t main_stream() override { return stream_.get(); }
 
     bool needs_input() override { return !finishing_; }
-    bool is_finished() override { return finishing_ && (done_ || rows_ == 0); }
+    bool is_finished() override { return finishing_ && (done_ || held_.rows == 0); }
     void finish() override { finishing_ = true; }
 
     // PagesIndex.addPage: the needed channels of the page behind the rows held so far; its buffers are the caller's again on return
@@ -132,41 +117,10 @@ public:
         PA_REQUIRE(page != nullptr && page->channel_count == (int32_t)types_.size(), PA_ERR_INVALID_ARGUMENT, "page does not match the input types");
         const int64_t m = page->position_count;
         if (m <= 0) return;
-        PA_REQUIRE(rows_ + m <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "more rows held than one sort takes");
+        PA_REQUIRE(held_.rows + m <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "more rows held than one sort takes");
         hipStream_t s = stream_.get();
         const DevPage in = stager_.stage(page, &needed_, s);
-        for (size_t c = 0; c < types_.size(); c++) {
-            if (!needed_[c]) continue;
-            const DevColumn& src = in.cols[c];
-            PA_REQUIRE(src.type == types_[c], PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared input type");
-            OutColumn& h = held_[c];
-            if (h.varwidth) {
-                int32_t ends[2];
-                PA_HIP(hipMemcpyAsync(&ends[0], src.offsets, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipMemcpyAsync(&ends[1], src.offsets + m, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                const int64_t add = ends[1] - ends[0];
-                PA_REQUIRE(add >= 0 && held_bytes_[c] + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "VARCHAR column exceeds 2 GB");
-                int32_t* off = static_cast<int32_t*>(h.offsets.reserve_keep((size_t)(rows_ + m + 1) * 4, (size_t)(rows_ ? rows_ + 1 : 0) * 4, s));
-                launch_offsets_append(src.offsets, m, (int32_t)held_bytes_[c], off + rows_, rows_ == 0, s);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(held_bytes_[c] + add + 1), (size_t)held_bytes_[c], s));
-                if (add) PA_HIP(hipMemcpyAsync(v + held_bytes_[c], static_cast<const char*>(src.values) + ends[0], (size_t)add, hipMemcpyDeviceToDevice, s));
-                held_bytes_[c] += add;
-            }
-            else {
-                const size_t w = (size_t)type_width(h.type);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(rows_ + m) * w, (size_t)rows_ * w, s));
-                PA_HIP(hipMemcpyAsync(v + (size_t)rows_ * w, src.values, (size_t)m * w, hipMemcpyDeviceToDevice, s));
-            }
-            if (src.nulls || h.has_nulls) {
-                uint8_t* nl = static_cast<uint8_t*>(h.nulls.reserve_keep((size_t)(rows_ + m), h.has_nulls ? (size_t)rows_ : 0, s));
-                if (!h.has_nulls && rows_ > 0) PA_HIP(hipMemsetAsync(nl, 0, (size_t)rows_, s));
-                if (src.nulls) PA_HIP(hipMemcpyAsync(nl + rows_, src.nulls, (size_t)m, hipMemcpyDeviceToDevice, s));
-                else PA_HIP(hipMemsetAsync(nl + rows_, 0, (size_t)m, s));
-                h.has_nulls = true;
-            }
-        }
-        rows_ += m;
+        held_.append_page(in, m, s);
         // the page's buffers are the caller's again, and the stager's are reused by the next page
         PA_HIP(hipStreamSynchronize(s));
     }
@@ -175,11 +129,11 @@ public:
     {
         if (!finishing_ || done_) return false;
         done_ = true;
-        if (rows_ == 0) return false;
+        if (held_.rows == 0) return false;
         hipStream_t s = stream_.get();
-        const int32_t n = (int32_t)rows_;
+        const int32_t n = (int32_t)held_.rows;
         std::vector<DevColumn> cols;
-        for (int32_t c : order_channels_) cols.push_back(view_of(held_[c]));
+        for (int32_t c : order_channels_) cols.push_back(held_.view(c));
         const int32_t* perm = sorter_.sort(cols, orders_, nullptr, 0, n, s);
         // runs: flags -> scans -> starts.  flags_: [part_flag | peer_flag | part_index | peer_index], starts_: [part_start | peer_start]
         int32_t* part_flag = static_cast<int32_t*>(flags_.ensure((size_t)n * 16));
@@ -188,7 +142,7 @@ public:
         int32_t* peer_index = part_index + n;
         int32_t* part_start = static_cast<int32_t*>(starts_.ensure(((size_t)n + 1) * 8));
         int32_t* peer_start = part_start + (n + (size_t)1);
-        int32_t* words = static_cast<int32_t*>(words_.ensure(64));   // [partition flags set, peer flags set, error]
+        int32_t* words = static_cast<int32_t*>(words_.ensure(64));   // [partition flags set, peer flags set, error, -, an output VARCHAR's bytes]
         void* scan_temp = scan_temp_.ensure(scan_temp_bytes(n));
         PA_HIP(hipMemsetAsync(part_flag, 0, (size_t)n * 8, s));
         PA_HIP(hipMemsetAsync(words, 0, 64, s));
@@ -224,7 +178,7 @@ public:
             oc.type = f.function == PA_WINDOW_PERCENT_RANK || f.function == PA_WINDOW_CUME_DIST ? PA_DOUBLE : PA_BIGINT;
             f.out = oc.values.ensure((size_t)n * 8);
             if (argument_channels_[k] < 0) continue;
-            const OutColumn& arg = held_[argument_channels_[k]];
+            const OutColumn& arg = held_.cols[argument_channels_[k]];
             f.arg_type = arg.type;
             f.arg_values = arg.values.ptr();
             if (arg.has_nulls) {
@@ -239,7 +193,8 @@ public:
         read_back(h_words, words, sizeof h_words, s);
         PA_REQUIRE(h_words[0] >= 0 && h_words[0] <= h_words[1] && h_words[1] < n, PA_ERR_DEVICE, "window: run counts out of range");
         PA_REQUIRE(h_words[2] == 0, PA_ERR_INVALID_ARGUMENT, "Buckets must be greater than 0");
-        gather_output(perm, n, s);
+        // the output channels in sorted order (PagesIndex.appendTo)
+        held_.gather_sorted(perm, n, output_channels_, nullptr, out_cols_, scan_temp_, words + 4, s);
         publish_output(out_cols_, n, output_mem_, s, out, storage_);
         return true;
     }
@@ -250,69 +205,17 @@ public:
     int64_t memory_bytes() override
     {
         size_t b = stager_.bytes() + sorter_.bytes() + flags_.capacity() + starts_.capacity() + words_.capacity() + scan_temp_.capacity();
-        for (const OutColumn& o : held_) b += o.values.capacity() + o.offsets.capacity() + o.nulls.capacity();
-        return (int64_t)b;
+        return (int64_t)(b + held_.bytes());
     }
 
 private:
-    // the output channels in sorted order (PagesIndex.appendTo): the fixed-width channels and every NULL flag array through the
-    // permutation by one launch per 24 columns, a VARCHAR channel by lengths -> scan -> copy
-    void gather_output(const int32_t* perm, int32_t n, hipStream_t s)
-    {
-        GatherMultiArgs gm;
-        memset(&gm, 0, sizeof gm);
-        gm.positions[0] = perm;
-        gm.count = n;
-        auto flush_gather = [&] {
-            if (gm.ncols > 0) launch_gather_multi(gm, s);
-            gm.ncols = 0;
-        };
-        for (size_t j = 0; j < output_channels_.size(); j++) {
-            const OutColumn& h = held_[output_channels_[j]];
-            OutColumn& oc = out_cols_[j];
-            oc.type = h.type;
-            oc.varwidth = h.varwidth;
-            const uint8_t* nulls = h.has_nulls ? h.nulls.as<uint8_t>() : nullptr;
-            oc.has_nulls = nulls != nullptr;
-            if (gm.ncols == GATHER_MULTI_MAX_COLS) flush_gather();
-            GatherMultiCol& gc = gm.col[gm.ncols];
-            memset(&gc, 0, sizeof gc);
-            gc.width = 1;
-            if (h.varwidth) {
-                int32_t* lens = static_cast<int32_t*>(oc.offsets.ensure(((size_t)n + 1) * 4));
-                int32_t* total = static_cast<int32_t*>(words_.ensure(64)) + 4;
-                launch_varwidth_lengths(perm, n, h.offsets.as<int32_t>(), nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, n, total, scan_temp_.ensure(scan_temp_bytes(n)), s);
-                int32_t h_total = 0;
-                read_back(&h_total, total, 4, s);
-                launch_varwidth_copy(perm, n, h.offsets.as<int32_t>(), h.values.as<uint8_t>(), nulls, lens,
-                                     static_cast<uint8_t*>(oc.values.ensure((size_t)(h_total > 0 ? h_total : 1))), total, s);
-            }
-            else {
-                const int w = type_width(h.type);   // (1, 4, 8, or 16 for a LONG_DECIMAL: creation refused every other type)
-                gc.src = h.values.ptr();
-                gc.dst = oc.values.ensure((size_t)n * w);
-                gc.width = w;
-            }
-            if (nulls) {
-                gc.src_nulls = nulls;
-                gc.dst_nulls = static_cast<uint8_t*>(oc.nulls.ensure((size_t)n));
-            }
-            if (gc.dst || gc.dst_nulls) gm.ncols++;
-        }
-        flush_gather();
-    }
-
     Stream stream_;
     PageStager stager_;
     std::vector<int32_t> types_, output_channels_, order_channels_, orders_, functions_, argument_channels_;
     size_t partition_count_ = 0;   // the first of order_channels_ are the partition channels
     std::vector<bool> needed_;
     int32_t output_mem_ = PA_MEM_HOST;
-    // the rows held, by input channel
-    std::vector<OutColumn> held_;
-    std::vector<int64_t> held_bytes_;   // VARCHAR bytes used
-    int64_t rows_ = 0;
+    HeldRows held_;
     RowSorter sorter_;
     DevBuf flags_, starts_, words_, scan_temp_;
     std::vector<OutColumn> out_cols_;

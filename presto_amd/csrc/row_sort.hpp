@@ -16,13 +16,6 @@
 
 namespace pa {
 
-// topn_kernels.hip (shared with op_order_by.cpp)
-void launch_sort_null_digits(const uint8_t* nulls, const int32_t* perm, int64_t n, int nulls_first, int32_t* digits, hipStream_t s);
-void launch_varchar_chunk_keys(const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int chunk, int descending, uint64_t* keys,
-                               hipStream_t s);
-void launch_iota_i32(int32_t* dst, int64_t n, hipStream_t s);
-int32_t varchar_max_length(const int32_t* offsets, int64_t n, void* temp_dev_8, hipStream_t s);
-
 class RowSorter {
 public:
     // cols / orders: the sort channels (pa_sort_order) over n rows, VARCHAR offsets starting at 0; gids (may be null): n group ids below

@@ -42,4 +42,14 @@ void launch_topn_tie_flags(const uint8_t* state, int64_t n, int32_t* flags, hipS
 // partition[i] = 0 for state 0 and for the first ties_kept rows in state 1 (tie_rank = exclusive scan of the tie flags), else 1
 void launch_topn_state_partition(const uint8_t* state, const int32_t* tie_rank, int64_t n, int64_t ties_kept, int32_t* partition, hipStream_t s);
 
+// The passes of a full sort by several channels (op_order_by.cpp, row_sort.hpp)
+// digits[i] = which side of the values the row perm[i] goes to: its NULL flag, turned round for NULLS FIRST
+void launch_sort_null_digits(const uint8_t* nulls, const int32_t* perm, int64_t n, int nulls_first, int32_t* digits, hipStream_t s);
+// keys[i] = the image of 8-byte chunk `chunk` of string i, zero padded (chunk -1: of its length)
+void launch_varchar_chunk_keys(const void* values, const int32_t* offsets, const uint8_t* nulls, int64_t n, int chunk, int descending, uint64_t* keys,
+                               hipStream_t s);
+void launch_iota_i32(int32_t* dst, int64_t n, hipStream_t s);
+// the longest string of a column; synchronises the stream
+int32_t varchar_max_length(const int32_t* offsets, int64_t n, void* temp_dev_8, hipStream_t s);
+
 }  // namespace pa

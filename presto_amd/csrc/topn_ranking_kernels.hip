@@ -2,7 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "topn_ranking_kernels.hpp"
-#include "kernels/pa_device.h"
+#include "kernels/pa_row_distinct.h"
 
 namespace pa {
 
@@ -42,39 +42,12 @@ __global__ __launch_bounds__(256) void k_topn_ranking_filter(const u64* __restri
     ((u32*)keep)[q] = w;   // (flags behind row n - 1 are never looked at)
 }
 
-// the bits under which two DOUBLEs are equal for Double.compare: one NaN
-__device__ __forceinline__ u64 double_identity(double d) { return d != d ? 0x7ff8000000000000ULL : (u64)__double_as_longlong(d); }
-__device__ __forceinline__ u32 float_identity(float f) { return f != f ? 0x7fc00000u : (u32)__float_as_int(f); }
-
-__device__ __forceinline__ bool rows_differ(i32 type, const void* __restrict__ values, const i32* __restrict__ offsets, const u8* __restrict__ nulls, i64 a, i64 b)
-{
-    const bool na = nulls && nulls[a], nb = nulls && nulls[b];
-    if (na || nb) return na != nb;
-    switch (type) {
-        case PA_BIGINT: return ((const i64*)values)[a] != ((const i64*)values)[b];
-        case PA_INTEGER:
-        case PA_DATE: return ((const i32*)values)[a] != ((const i32*)values)[b];
-        case PA_BOOLEAN: return (((const u8*)values)[a] != 0) != (((const u8*)values)[b] != 0);
-        case PA_DOUBLE: return double_identity(((const double*)values)[a]) != double_identity(((const double*)values)[b]);
-        case PA_REAL: return float_identity(((const float*)values)[a]) != float_identity(((const float*)values)[b]);
-        case PA_VARCHAR: {
-            const i32 oa = offsets[a], ob = offsets[b], la = offsets[a + 1] - oa, lb = offsets[b + 1] - ob;
-            if (la != lb) return true;
-            const u8* pa_ = (const u8*)values + oa;
-            const u8* pb_ = (const u8*)values + ob;
-            for (i32 j = 0; j < la; j++)
-                if (pa_[j] != pb_[j]) return true;
-            return false;
-        }
-        default: return true;
-    }
-}
-
+// differs from the sorted row before under the comparator's identity: one NaN, two zeros
 __global__ __launch_bounds__(256) void k_topn_ranking_differs(i32 type, const void* __restrict__ values, const i32* __restrict__ offsets,
                                                               const u8* __restrict__ nulls, const i32* __restrict__ perm, i32 n, u8* __restrict__ differs)
 {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x + 1; i < n; i += (i64)gridDim.x * 256)
-        if (rows_differ(type, values, offsets, nulls, perm[i - 1], perm[i])) differs[i] = 1;
+        if (row_distinct<false>(type, values, offsets, nulls, perm[i - 1], perm[i])) differs[i] = 1;
 }
 
 __global__ __launch_bounds__(256) void k_topn_ranking_heads(const u64* __restrict__ gids, const u8* __restrict__ differs, i32 n, i32* __restrict__ run_start,

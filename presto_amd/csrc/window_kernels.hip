@@ -2,49 +2,18 @@
 #include <hip/hip_runtime.h>
 
 #include "window_kernels.hpp"
-#include "kernels/pa_device.h"
+#include "kernels/pa_row_distinct.h"
 
 namespace pa {
 
 namespace {
 
-// IS DISTINCT FROM of two rows in one channel (the rules of the header: not the comparator's, under which -0.0 differs from +0.0)
-__device__ __forceinline__ bool rows_distinct(i32 type, const void* __restrict__ values, const i32* __restrict__ offsets, const u8* __restrict__ nulls, i64 a, i64 b)
-{
-    const bool na = nulls && nulls[a], nb = nulls && nulls[b];
-    if (na || nb) return na != nb;
-    switch (type) {
-        case PA_BIGINT:
-        case PA_DECIMAL: return ((const i64*)values)[a] != ((const i64*)values)[b];
-        case PA_INTEGER:
-        case PA_DATE: return ((const i32*)values)[a] != ((const i32*)values)[b];
-        case PA_BOOLEAN: return (((const u8*)values)[a] != 0) != (((const u8*)values)[b] != 0);
-        case PA_DOUBLE: {
-            const double x = ((const double*)values)[a], y = ((const double*)values)[b];
-            return !(x == y || (x != x && y != y));
-        }
-        case PA_REAL: {
-            const float x = ((const float*)values)[a], y = ((const float*)values)[b];
-            return !(x == y || (x != x && y != y));
-        }
-        case PA_VARCHAR: {
-            const i32 oa = offsets[a], ob = offsets[b], la = offsets[a + 1] - oa, lb = offsets[b + 1] - ob;
-            if (la != lb) return true;
-            const u8* pa_ = (const u8*)values + oa;
-            const u8* pb_ = (const u8*)values + ob;
-            for (i32 j = 0; j < la; j++)
-                if (pa_[j] != pb_[j]) return true;
-            return false;
-        }
-        default: return true;
-    }
-}
-
+// IS DISTINCT FROM the sorted row before, per channel (not the comparator's rule, under which -0.0 differs from +0.0)
 __global__ __launch_bounds__(256) void k_window_distinct(i32 type, const void* __restrict__ values, const i32* __restrict__ offsets, const u8* __restrict__ nulls,
                                                          const i32* __restrict__ perm, i32 n, i32* __restrict__ flag_a, i32* __restrict__ flag_b)
 {
     for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x + 1; i < n; i += (i64)gridDim.x * 256) {
-        if (!rows_distinct(type, values, offsets, nulls, perm[i - 1], perm[i])) continue;
+        if (!row_distinct<true>(type, values, offsets, nulls, perm[i - 1], perm[i])) continue;
         flag_a[i] = 1;
         if (flag_b) flag_b[i] = 1;
     }
