@@ -549,7 +549,8 @@ typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingTy
  * BY k ... ORDER BY x ...)`, planned by LocalExecutionPlanner.visitWindow (WindowOperator.java over RegularWindowPartition and the
  * functions of operator/window/).  These six ignore frames.  Value functions (lag, lead, first_value, last_value, nth_value), aggregate
  * window functions, frames, pre-grouped / pre-sorted input, spill and pattern recognition have no id here: the caller keeps the
- * reference operator for a window node that uses one.
+ * reference operator for a window node that uses one.  count / sum / min / max over the frames that start at UNBOUNDED PRECEDING live
+ * in the framed form of this descriptor, pa_framed_window_desc below (pa_framed_window_create); ids above 5 stay unknown here.
  *   Order: the rows are sorted by SimplePageWithPositionComparator over [partition channels, each ASC_NULLS_LAST] + [sort channels with
  *     their orders] (WindowOperator.java:294), under the rules of pa_order_by_desc.  Rows that compare equal on all of those channels
  *     stay in arrival order (the reference's sort leaves this open; it is what TopN, OrderBy and TopNRanking promise here too).
@@ -587,7 +588,9 @@ typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingTy
  *   More than INT32_MAX rows held, or the pool limit reached: PA_ERR_INSUFFICIENT_RESOURCES.  pa_op_memory_bytes reports the rows held
  *     (+ scratch while allocated). */
 typedef enum pa_window_function {
-    PA_WINDOW_ROW_NUMBER = 0, PA_WINDOW_RANK = 1, PA_WINDOW_DENSE_RANK = 2, PA_WINDOW_PERCENT_RANK = 3, PA_WINDOW_CUME_DIST = 4, PA_WINDOW_NTILE = 5
+    PA_WINDOW_ROW_NUMBER = 0, PA_WINDOW_RANK = 1, PA_WINDOW_DENSE_RANK = 2, PA_WINDOW_PERCENT_RANK = 3, PA_WINDOW_CUME_DIST = 4, PA_WINDOW_NTILE = 5,
+    /* the aggregates: pa_framed_window_desc only */
+    PA_WINDOW_COUNT_STAR = 6, PA_WINDOW_COUNT = 7, PA_WINDOW_SUM = 8, PA_WINDOW_MIN = 9, PA_WINDOW_MAX = 10
 } pa_window_function;
 typedef struct pa_window_function_desc {
     int32_t function;                    /* pa_window_function */
@@ -614,6 +617,71 @@ typedef struct pa_window_desc {          /* WindowOperatorFactory(sourceTypes, o
     int32_t output_mem;                  /* pa_mem */
     void* stream;
 } pa_window_desc;
+
+/* WindowOperator with frames: pa_window_desc whose functions carry a frame (FrameInfo), for the aggregate window functions count(*) /
+ * count(x) / sum(x) / min(x) / max(x) next to the six ranking functions.  It builds the same operator: order, partitions, peers, the
+ * output layout, the state machine, the refusal of pre-grouped / pre-sorted input and the limits of 8 partition channels and 16
+ * functions are those of pa_window_desc, unchanged.  For ids 0 .. 5 the frame is range-checked and otherwise ignored, and the column is
+ * bit for bit the one pa_window_create gives: a window node that mixes rank() with sum() runs in one operator and one sort.
+ *   Frames: start_type must be PA_BOUND_UNBOUNDED_PRECEDING.  With i the row's place in its partition, N the partition's size and
+ *     [ps, pe) its peer group's places, the frame of an aggregate is the places 0 .. e:
+ *       PA_FRAME_ROWS   ... PA_BOUND_CURRENT_ROW                     e = i
+ *       PA_FRAME_RANGE / PA_FRAME_GROUPS ... PA_BOUND_CURRENT_ROW    e = pe - 1     (RANGE is the SQL default frame)
+ *       any type        ... PA_BOUND_UNBOUNDED_FOLLOWING             e = N - 1
+ *     These frames are never empty.  Every other well-formed frame of an aggregate is PA_ERR_NOT_SUPPORTED at creation.
+ *   Functions, over the frame's rows in sorted order ("non-null": the argument is not NULL at that row):
+ *       PA_WINDOW_COUNT_STAR  no argument                                    BIGINT e + 1, never NULL
+ *       PA_WINDOW_COUNT       one channel of any type an output channel may have (only its NULLs are read)
+ *                                                                            BIGINT count of the non-null rows, never NULL
+ *       PA_WINDOW_SUM         BIGINT or INTEGER                              BIGINT; NULL when the frame has no non-null row
+ *       PA_WINDOW_MIN / MAX   BIGINT, INTEGER, DATE, BOOLEAN, short DECIMAL, DOUBLE, REAL
+ *                                                                            the argument's type; NULL when the frame has no non-null row
+ *     sum (LongSumAggregation) adds with Math.addExact in sorted order whatever the frame: when ANY prefix sum of the non-null values of
+ *     any partition leaves int64 -- also when a later row brings it back in range -- the first pa_op_get_output after finish fails with
+ *     PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, nothing is emitted, and the operator can still be closed and destroyed.  Partitions never affect
+ *     each other.  Which error is reported when a bad ntile bucket count occurs in the same run is not part of the contract.
+ *     min / max (AbstractMinMaxAggregationFunction with MinMaxCompare) replace the held value only by a strictly better one, so of equal
+ *     values the first in sorted order stays.  Better: min, every type: compares < 0, for DOUBLE / REAL in Double.compare order (-0.0
+ *     before +0.0, NaN largest); max over DOUBLE / REAL: value > held || isNaN(held) (NaN loses to everything, -0.0 and +0.0 tie).  A NaN
+ *     result is some NaN: its payload is not part of the contract.  A BOOLEAN result is 0 or 1.
+ *   At creation, before any device work, PA_ERR_INVALID_ARGUMENT first: what pa_window_desc reports; a function id outside 0 .. 10; a
+ *     frame_type, start_type or end_type outside its enum; start_type PA_BOUND_UNBOUNDED_FOLLOWING; end_type
+ *     PA_BOUND_UNBOUNDED_PRECEDING; a PA_BOUND_PRECEDING / PA_BOUND_FOLLOWING bound whose channel is out of range; ignore_nulls != 0; a
+ *     wrong argument_count; a sum argument that is not numeric (VARCHAR, BOOLEAN, DATE).  Then PA_ERR_NOT_SUPPORTED: what pa_window_desc
+ *     refuses; any other frame of an aggregate; sum over DOUBLE, REAL, DECIMAL or a long decimal; min / max over VARCHAR, a long decimal
+ *     or PA_ROW; count over PA_ROW.  Value functions (lag, lead, first_value, last_value, nth_value), avg and IGNORE NULLS have no id. */
+typedef enum pa_window_frame_type { PA_FRAME_RANGE = 0, PA_FRAME_ROWS = 1, PA_FRAME_GROUPS = 2 } pa_window_frame_type;
+typedef enum pa_window_frame_bound {
+    PA_BOUND_UNBOUNDED_PRECEDING = 0, PA_BOUND_PRECEDING = 1, PA_BOUND_CURRENT_ROW = 2, PA_BOUND_FOLLOWING = 3, PA_BOUND_UNBOUNDED_FOLLOWING = 4
+} pa_window_frame_bound;
+typedef struct pa_framed_window_function_desc {
+    int32_t function;                    /* pa_window_function, 0 .. 10 */
+    int32_t argument_count;              /* ntile, count, sum, min, max: 1; else 0 */
+    const int32_t* argument_channels;    /* may be NULL when there are none */
+    int32_t frame_type;                  /* FrameInfo.getType as a pa_window_frame_type */
+    int32_t start_type, start_channel;   /* pa_window_frame_bound; channel -1 when the bound takes none */
+    int32_t end_type, end_channel;
+    int32_t ignore_nulls;                /* must be 0 */
+} pa_framed_window_function_desc;
+typedef struct pa_framed_window_desc {   /* the fields of pa_window_desc, in the same order */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;
+    int32_t output_channel_count;
+    const int32_t* output_channels;
+    int32_t function_count;              /* 1 .. 16 */
+    const pa_framed_window_function_desc* functions;
+    int32_t partition_channel_count;
+    const int32_t* partition_channels;
+    int32_t sort_channel_count;
+    const int32_t* sort_channels;
+    const int32_t* sort_orders;
+    int32_t pre_grouped_channel_count;   /* must be 0 */
+    int32_t pre_sorted_channel_prefix;   /* must be 0 */
+    int32_t expected_positions;
+    int32_t output_mem;
+    void* stream;
+} pa_framed_window_desc;
 
 /* Fused pipeline: [Scan]FilterAndProject -> LookupJoinOperator -> (Hash)AggregationOperator, the probe side of a join whose
  * output is only ever aggregated (TPC-H Q3's lineitem pipeline; LocalExecutionPlanner chains exactly these three operator
@@ -855,6 +923,8 @@ int32_t pa_topn_ranking_create(const pa_topn_ranking_desc* desc, pa_operator** o
 int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity, int64_t* rows_held);
 /* Window (pa_window_desc above). */
 int32_t pa_window_create(const pa_window_desc* desc, pa_operator** out);
+/* Window with frames: the ranking functions and count / sum / min / max (pa_framed_window_desc above). */
+int32_t pa_framed_window_create(const pa_framed_window_desc* desc, pa_operator** out);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

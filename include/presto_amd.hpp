@@ -642,6 +642,69 @@ struct WindowOperatorFactory {
     }
 };
 
+// The same factory over pa_framed_window_desc: the ranking functions and count(*) / count / sum / min / max, each with its frame
+// (FrameInfo); without one, the SQL default RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
+struct FramedWindowFunctionDefinition {
+    int32_t function = PA_WINDOW_ROW_NUMBER;   // pa_window_function, 0 .. 10
+    std::vector<int32_t> argumentChannels;     // ntile, count, sum, min, max: one channel
+    int32_t frameType = PA_FRAME_RANGE, startType = PA_BOUND_UNBOUNDED_PRECEDING, endType = PA_BOUND_CURRENT_ROW;
+    int32_t startChannel = -1, endChannel = -1;
+    bool ignoreNulls = false;
+};
+struct FramedWindowOperatorFactory {
+    std::vector<int32_t> sourceTypes, outputChannels;
+    std::vector<FramedWindowFunctionDefinition> functions;
+    std::vector<int32_t> partitionChannels, sortChannels, sortOrders;
+    int32_t preGroupedChannelCount = 0, preSortedChannelPrefix = 0, expectedPositions = 0, outputMem = PA_MEM_HOST;
+    std::vector<int32_t> typeParams;
+
+    FramedWindowOperatorFactory(std::vector<int32_t> sourceTypes, std::vector<int32_t> outputChannels, std::vector<FramedWindowFunctionDefinition> functions,
+                                std::vector<int32_t> partitionChannels, std::vector<int32_t> sortChannels, std::vector<int32_t> sortOrders,
+                                int32_t expectedPositions = 0, int32_t outputMem = PA_MEM_HOST)
+        : sourceTypes(std::move(sourceTypes)), outputChannels(std::move(outputChannels)), functions(std::move(functions)),
+          partitionChannels(std::move(partitionChannels)), sortChannels(std::move(sortChannels)), sortOrders(std::move(sortOrders)),
+          expectedPositions(expectedPositions), outputMem(outputMem)
+    {
+    }
+
+    std::unique_ptr<Operator> createOperator() const
+    {
+        std::vector<pa_framed_window_function_desc> fs(functions.size());
+        for (size_t i = 0; i < functions.size(); i++) {
+            const FramedWindowFunctionDefinition& f = functions[i];
+            fs[i].function = f.function;
+            fs[i].argument_count = (int32_t)f.argumentChannels.size();
+            fs[i].argument_channels = f.argumentChannels.data();
+            fs[i].frame_type = f.frameType;
+            fs[i].start_type = f.startType;
+            fs[i].start_channel = f.startChannel;
+            fs[i].end_type = f.endType;
+            fs[i].end_channel = f.endChannel;
+            fs[i].ignore_nulls = f.ignoreNulls ? 1 : 0;
+        }
+        pa_framed_window_desc d{};
+        d.input_channel_count = (int32_t)sourceTypes.size();
+        d.input_types = sourceTypes.data();
+        d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        d.output_channel_count = (int32_t)outputChannels.size();
+        d.output_channels = outputChannels.data();
+        d.function_count = (int32_t)fs.size();
+        d.functions = fs.data();
+        d.partition_channel_count = (int32_t)partitionChannels.size();
+        d.partition_channels = partitionChannels.data();
+        d.sort_channel_count = (int32_t)sortChannels.size();
+        d.sort_channels = sortChannels.data();
+        d.sort_orders = sortOrders.data();
+        d.pre_grouped_channel_count = preGroupedChannelCount;
+        d.pre_sorted_channel_prefix = preSortedChannelPrefix;
+        d.expected_positions = expectedPositions;
+        d.output_mem = outputMem;
+        pa_operator* h = nullptr;
+        check(pa_framed_window_create(&d, &h));
+        return std::make_unique<Operator>(h);
+    }
+};
+
 // OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; filter = the join's
 // JoinFilterFunction over [build page channels, probe page channels], or null
 inline std::unique_ptr<Operator> createLookupJoinOperator(LookupSourceFactory& bridge, const std::vector<int32_t>& probeTypes,

@@ -96,6 +96,11 @@ final class GpuNative
     static native long createWindow(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] functions, int[] functionArguments,
             int[] partitionChannels, int[] sortChannels, int[] sortOrders, int preGroupedChannelCount, int preSortedChannelPrefix,
             int expectedPositions, int outputMem);
+    /** The same with frames: the ranking functions and count / sum / min / max (ids 6 .. 10).  frames = six ints per function:
+     *  frame type, start type, start channel, end type, end channel, ignore nulls (FrameInfo; pa_framed_window_function_desc). */
+    static native long createFramedWindow(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] functions, int[] functionArguments,
+            int[] frames, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int preGroupedChannelCount, int preSortedChannelPrefix,
+            int expectedPositions, int outputMem);
     static native long createTopN(int[] inputTypes, int count, int[] sortChannels, int[] sortOrders, int outputMem);
     static native boolean setDynamicFilter(long filterProjectOperator, int channel, long lookupSource);
 

@@ -696,6 +696,41 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createWindow(JNIEnv* env, jc
     return (jlong)(intptr_t)op;
 }
 
+/* The same with frames (pa_framed_window_desc): the ranking functions and count / sum / min / max.  frames = six ints per function:
+ * frame_type, start_type, start_channel, end_type, end_channel, ignore_nulls (pa_window_frame_type / pa_window_frame_bound). */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createFramedWindow(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams, jintArray outputChannels,
+        jintArray functions, jintArray functionArguments, jintArray frames, jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders,
+        jint preGroupedChannelCount, jint preSortedChannelPrefix, jint expectedPositions, jint outputMem)
+{
+    jsize n, no, nf, nfa, nfr, npc, nsc, nso, np_ = 0, i;
+    pa_framed_window_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *oc = ints_of(env, outputChannels, &no), *fn = ints_of(env, functions, &nf);
+    int32_t *fa = ints_of(env, functionArguments, &nfa), *fr = ints_of(env, frames, &nfr), *pc = ints_of(env, partitionChannels, &npc);
+    int32_t *sc = ints_of(env, sortChannels, &nsc), *so = ints_of(env, sortOrders, &nso);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    if (nf != nfa || nfr != 6 * nf) nf = 0;   /* (refused below: function_count 0) */
+    pa_framed_window_function_desc* fs = (pa_framed_window_function_desc*)calloc((size_t)(nf > 0 ? nf : 1), sizeof *fs);
+    for (i = 0; fs && fn && fa && fr && i < nf; i++) {
+        fs[i].function = fn[i];
+        fs[i].argument_count = fa[i] >= 0 ? 1 : 0;
+        fs[i].argument_channels = fa + i;
+        fs[i].frame_type = fr[6 * i]; fs[i].start_type = fr[6 * i + 1]; fs[i].start_channel = fr[6 * i + 2];
+        fs[i].end_type = fr[6 * i + 3]; fs[i].end_channel = fr[6 * i + 4]; fs[i].ignore_nulls = fr[6 * i + 5];
+    }
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.output_channel_count = no; d.output_channels = oc; d.function_count = fs && fr ? nf : 0; d.functions = fs;
+    d.partition_channel_count = npc; d.partition_channels = pc;
+    d.sort_channel_count = nsc == nso ? nsc : -1; d.sort_channels = sc; d.sort_orders = so;
+    d.pre_grouped_channel_count = preGroupedChannelCount; d.pre_sorted_channel_prefix = preSortedChannelPrefix;
+    d.expected_positions = expectedPositions; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_framed_window_create(&d, &op);
+    free(fs); free(params); free(so); free(sc); free(pc); free(fr); free(fa); free(fn); free(oc); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
 /* OperatorFactories.innerJoin / probeOuterJoin / lookupOuterJoin / fullOuterJoin: joinType = pa_join_type; outer = 1 creates the
  * LookupOuterOperator of the same bridge; filter = a newExpression handle over [build channels, probe channels] (the
  * JoinFilterFunction the planner compiled for this join, JoinFilterFunctionCompiler.java) or 0 */

@@ -428,6 +428,30 @@ class pa_window_desc(C.Structure):
     ]
 
 
+# the aggregates and the frames of pa_framed_window_desc
+WINDOW_COUNT_STAR, WINDOW_COUNT, WINDOW_SUM, WINDOW_MIN, WINDOW_MAX = 6, 7, 8, 9, 10                                # pa_window_function
+FRAME_RANGE, FRAME_ROWS, FRAME_GROUPS = 0, 1, 2                                                                     # pa_window_frame_type
+BOUND_UNBOUNDED_PRECEDING, BOUND_PRECEDING, BOUND_CURRENT_ROW, BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4   # pa_window_frame_bound
+
+
+class pa_framed_window_function_desc(C.Structure):
+    _fields_ = [
+        ("function", C.c_int32),
+        ("argument_count", C.c_int32),
+        ("argument_channels", C.POINTER(C.c_int32)),
+        ("frame_type", C.c_int32),
+        ("start_type", C.c_int32),
+        ("start_channel", C.c_int32),
+        ("end_type", C.c_int32),
+        ("end_channel", C.c_int32),
+        ("ignore_nulls", C.c_int32),
+    ]
+
+
+class pa_framed_window_desc(C.Structure):
+    _fields_ = [(name, C.POINTER(pa_framed_window_function_desc) if name == "functions" else t) for name, t in pa_window_desc._fields_]
+
+
 class pa_fused_join_desc(C.Structure):
     _fields_ = [
         ("filter_project", pa_filter_project_desc),

@@ -686,6 +686,14 @@ int32_t pa_window_create(const pa_window_desc* desc, pa_operator** out)
         return PA_OK;
     });
 }
+int32_t pa_framed_window_create(const pa_framed_window_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_framed_window(desc);
+        return PA_OK;
+    });
+}
 
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)

@@ -81,6 +81,8 @@ pa_operator* make_topn_ranking(const pa_topn_ranking_desc* desc);
 void topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity, int64_t* rows_held);
 // WindowOperator, the ranking functions (op_window.cpp)
 pa_operator* make_window(const pa_window_desc* desc);
+// the same operator from the framed descriptor: the ranking functions and count / sum / min / max
+pa_operator* make_framed_window(const pa_framed_window_desc* desc);
 // the consumer of an aggregation's output is a TopN over it: groups that cannot be among its n best rows may be left out (op_fused.cpp, op_fused_output.cpp);
 // false: the operator does not take the hint (it emits everything)
 bool aggregation_set_output_topn(pa_operator* op, int64_t n, const int32_t* sort_channels, const int32_t* sort_orders, int32_t count);

@@ -34,6 +34,198 @@ __global__ __launch_bounds__(256) void k_window_starts(const i32* __restrict__ p
     }
 }
 
+// ---- the aggregates: gather, segmented scans ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_window_gather(i32 type, const void* __restrict__ values, const u8* __restrict__ nulls, const i32* __restrict__ perm, i32 n,
+                                                       u64* __restrict__ sorted_values, u8* __restrict__ sorted_nulls)
+{
+    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) {
+        const i64 row = perm[i];
+        if (sorted_nulls) sorted_nulls[i] = nulls[row] ? (u8)1 : (u8)0;
+        if (!sorted_values) continue;
+        u64 v;
+        switch (type) {
+            case PA_INTEGER:
+            case PA_DATE: v = (u64)(i64)((const i32*)values)[row]; break;
+            case PA_BOOLEAN: v = ((const u8*)values)[row] ? 1ULL : 0ULL; break;
+            case PA_REAL: v = (u64)__double_as_longlong((double)((const float*)values)[row]); break;
+            default: v = ((const u64*)values)[row]; break;   // BIGINT, short DECIMAL, DOUBLE
+        }
+        sorted_values[i] = v;
+    }
+}
+
+// The state of a scan with the flag "a partition starts here or before, inside what this state covers".  count: b = the non-null rows;
+// sum: (b, a) = the 96-bit sum, a its low word (n <= INT32_MAX values of 64 bits: exact); min / max: a = the held value, b = there is one.
+struct WindowAcc {
+    u64 a;
+    i32 b;
+    i32 f;
+};
+// how min / max compare: the key of a value under the mode; the held value is replaced when the new key is smaller (min) / greater (max)
+enum { kCmpInt = 0, kCmpDoubleMin = 1, kCmpDoubleMax = 2 };
+__device__ __forceinline__ i64 minmax_key(u64 bits, int mode)
+{
+    if (mode == kCmpInt) return (i64)bits;
+    const bool nan = (bits & 0x7FFFFFFFFFFFFFFFULL) > 0x7FF0000000000000ULL;
+    const i64 b = (i64)bits;
+    const i64 image = b < 0 ? (b ^ 0x7FFFFFFFFFFFFFFFLL) : b;   // Double.compare order of the non-NaN values: -0.0 -> -1, +0.0 -> 0
+    if (mode == kCmpDoubleMin) return nan ? 0x7FFFFFFFFFFFFFFFLL : image;   // NaN largest
+    return nan ? (i64)0x8000000000000000ULL : (image == -1 ? 0 : image);    // max: NaN loses to everything (-inf included), the zeros tie
+}
+// x (f1, v1) before y (f2, v2): (f1 | f2, f2 ? v2 : v1 + v2)
+template <int KIND>
+__device__ __forceinline__ WindowAcc acc_combine(WindowAcc x, WindowAcc y, int mode)
+{
+    // (selects field by field, no early return: a choice between two structs would leave them in scratch)
+    const bool restart = y.f != 0;
+    WindowAcc r;
+    r.f = x.f | y.f;
+    if (KIND == kWindowScanCount) {
+        r.a = 0;
+        r.b = restart ? y.b : x.b + y.b;
+    }
+    else if (KIND == kWindowScanSum) {
+        const u64 lo = x.a + y.a;
+        r.a = restart ? y.a : lo;
+        r.b = restart ? y.b : x.b + y.b + (lo < x.a ? 1 : 0);
+    }
+    else {
+        const i64 kx = minmax_key(x.a, mode), ky = minmax_key(y.a, mode);
+        const bool better = KIND == kWindowScanMin ? ky < kx : ky > kx;
+        // keep the left unless there is none or the right is strictly better
+        const bool take = restart || !x.b || (y.b && better);
+        r.a = take ? y.a : x.a;
+        r.b = take ? y.b : x.b;
+    }
+    return r;
+}
+template <int KIND>
+__device__ __forceinline__ WindowAcc acc_shfl_up(const WindowAcc& v, int off)
+{
+    WindowAcc o;
+    o.a = KIND == kWindowScanCount ? 0 : (u64)__shfl_up((long long)v.a, off, 64);
+    o.b = __shfl_up(v.b, off, 64);
+    o.f = __shfl_up(v.f, off, 64);
+    return o;
+}
+__device__ __forceinline__ WindowAcc acc_identity()
+{
+    WindowAcc r;
+    r.a = 0;
+    r.b = 0;
+    r.f = 0;
+    return r;
+}
+
+// The four consecutive entries of a lane, combined in place (s[j] = e[0] + ... + e[j]), then over the 256 lanes of the workgroup: the
+// state of everything in front of the lane's entries inside the workgroup (returned) and of the whole workgroup (*total).
+template <int KIND>
+__device__ __forceinline__ WindowAcc acc_block_scan(WindowAcc (&s)[4], int mode, WindowAcc* total)
+{
+    __shared__ WindowAcc wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 1; j < 4; j++) s[j] = acc_combine<KIND>(s[j - 1], s[j], mode);
+    WindowAcc inc = s[3];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const WindowAcc o = acc_shfl_up<KIND>(inc, off);
+        if (lane >= off) inc = acc_combine<KIND>(o, inc, mode);
+    }
+    if (lane == 63) wave_total[wave] = inc;
+    WindowAcc before = acc_shfl_up<KIND>(inc, 1);
+    if (lane == 0) before = acc_identity();
+    __syncthreads();
+    WindowAcc front = acc_identity(), all = acc_identity();
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const WindowAcc t = wave_total[w];
+        if (w < wave) front = acc_combine<KIND>(front, t, mode);
+        all = acc_combine<KIND>(all, t, mode);
+    }
+    __syncthreads();
+    *total = all;
+    return acc_combine<KIND>(front, before, mode);
+}
+
+// the entries of sorted rows base .. base + 3 (rows at or past n: the identity)
+template <int KIND>
+__device__ __forceinline__ void acc_load_rows(WindowAcc (&s)[4], i64 base, i32 n, const u64* __restrict__ values, const u8* __restrict__ nulls,
+                                              const i32* __restrict__ part_flag)
+{
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const i64 i = base + j;
+        s[j] = acc_identity();
+        if (i >= n) continue;
+        const bool is_null = nulls && nulls[i];
+        s[j].f = part_flag[i];
+        if (KIND == kWindowScanCount) s[j].b = is_null ? 0 : 1;
+        else if (KIND == kWindowScanSum) {
+            const i64 v = is_null ? 0 : (i64)values[i];
+            s[j].a = (u64)v;
+            s[j].b = v < 0 ? -1 : 0;
+        }
+        else {
+            s[j].a = values[i];
+            s[j].b = is_null ? 0 : 1;
+        }
+    }
+}
+
+// launch 1 of 3: the state of every tile of kWindowScanTile rows
+template <int KIND>
+__global__ __launch_bounds__(256) void k_window_scan_tiles(const u64* __restrict__ values, const u8* __restrict__ nulls, const i32* __restrict__ part_flag, i32 n,
+                                                           int mode, WindowAcc* __restrict__ tile_acc)
+{
+    WindowAcc s[4], total;
+    acc_load_rows<KIND>(s, (i64)blockIdx.x * kWindowScanTile + (i64)threadIdx.x * 4, n, values, nulls, part_flag);
+    (void)acc_block_scan<KIND>(s, mode, &total);
+    if (threadIdx.x == 0) tile_acc[blockIdx.x] = total;
+}
+
+// launch 2 of 3, one workgroup: tile_front[t] = the state of the tiles in front of tile t, kWindowScanTile tiles at a time
+template <int KIND>
+__global__ __launch_bounds__(256) void k_window_scan_tile_fronts(const WindowAcc* __restrict__ tile_acc, i32 tiles, int mode, WindowAcc* __restrict__ tile_front)
+{
+    WindowAcc carry = acc_identity();
+    for (i32 chunk = 0; chunk < tiles; chunk += kWindowScanTile) {
+        const i32 base = chunk + (i32)threadIdx.x * 4;
+        WindowAcc e[4], s[4], total;
+#pragma unroll
+        for (int j = 0; j < 4; j++) s[j] = e[j] = base + j < tiles ? tile_acc[base + j] : acc_identity();
+        WindowAcc front = acc_combine<KIND>(carry, acc_block_scan<KIND>(s, mode, &total), mode);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (base + j < tiles) tile_front[base + j] = front;
+            front = acc_combine<KIND>(front, e[j], mode);
+        }
+        carry = acc_combine<KIND>(carry, total, mode);
+    }
+}
+
+// launch 3 of 3: the tile's own scan behind the state in front of it; a prefix sum outside int64 sets its bit of the error word
+template <int KIND>
+__global__ __launch_bounds__(256) void k_window_scan_apply(const u64* __restrict__ values, const u8* __restrict__ nulls, const i32* __restrict__ part_flag, i32 n,
+                                                           int mode, const WindowAcc* __restrict__ tile_front, void* __restrict__ out, i32* __restrict__ error)
+{
+    const i64 base = (i64)blockIdx.x * kWindowScanTile + (i64)threadIdx.x * 4;
+    WindowAcc s[4], total;
+    acc_load_rows<KIND>(s, base, n, values, nulls, part_flag);
+    const WindowAcc front = acc_combine<KIND>(tile_front[blockIdx.x], acc_block_scan<KIND>(s, mode, &total), mode);
+    bool overflow = false;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const i64 i = base + j;
+        if (i >= n) continue;
+        const WindowAcc r = acc_combine<KIND>(front, s[j], mode);
+        if (KIND == kWindowScanCount) ((i32*)out)[i] = r.b;
+        else ((u64*)out)[i] = r.a;
+        if (KIND == kWindowScanSum && r.b != ((i64)r.a < 0 ? -1 : 0)) overflow = true;
+    }
+    if (KIND == kWindowScanSum && overflow) atomicOr(error, kWindowErrorSum);
+}
+
 // NTileFunction.bucket in int64: place i of a partition of N rows
 __device__ __forceinline__ i64 ntile_bucket(i64 i, i64 N, i64 buckets)
 {
@@ -74,11 +266,37 @@ __global__ __launch_bounds__(256) void k_window_functions(WindowFunctionArgs a)
                     i64 value = 0;
                     if (!is_null) {
                         const i64 buckets = f.arg_type == PA_BIGINT ? ((const i64*)f.arg_values)[row] : (i64)((const i32*)f.arg_values)[row];
-                        if (buckets <= 0) atomicOr(a.error, 1);
+                        if (buckets <= 0) atomicOr(a.error, kWindowErrorBuckets);
                         else value = ntile_bucket(place, N, buckets) + 1;
                     }
                     ((i64*)f.out)[i] = value;
                     if (f.out_nulls) f.out_nulls[i] = is_null ? (u8)1 : (u8)0;
+                    break;
+                }
+                case PA_WINDOW_COUNT_STAR:
+                case PA_WINDOW_COUNT:
+                case PA_WINDOW_SUM:
+                case PA_WINDOW_MIN:
+                case PA_WINDOW_MAX: {
+                    // the frame is places 0 .. e; its state stands at sorted row first + e, inside [i, n)
+                    const i64 e = f.frame_end == kWindowFrameRow ? place : f.frame_end == kWindowFramePeers ? pe - 1 : N - 1;
+                    i64 at = first + e;
+                    at = at < i ? i : at > (i64)n - 1 ? (i64)n - 1 : at;
+                    const i64 rows = f.count ? (i64)f.count[at] : e + 1;   // the frame's non-null rows
+                    if (f.function == PA_WINDOW_COUNT_STAR) ((i64*)f.out)[i] = e + 1;
+                    else if (f.function == PA_WINDOW_COUNT) ((i64*)f.out)[i] = rows;
+                    else {
+                        const u64 v = rows > 0 ? ((const u64*)f.scan)[at] : 0ULL;
+                        if (f.function == PA_WINDOW_SUM) ((u64*)f.out)[i] = v;
+                        else switch (f.arg_type) {
+                            case PA_INTEGER:
+                            case PA_DATE: ((i32*)f.out)[i] = (i32)(i64)v; break;
+                            case PA_REAL: ((float*)f.out)[i] = (float)__longlong_as_double((long long)v); break;
+                            case PA_BOOLEAN: ((u8*)f.out)[i] = (u8)v; break;
+                            default: ((u64*)f.out)[i] = v; break;
+                        }
+                        if (f.out_nulls) f.out_nulls[i] = rows > 0 ? (u8)0 : (u8)1;
+                    }
                     break;
                 }
                 default: break;
@@ -111,6 +329,45 @@ void launch_window_starts(const int32_t* part_flag, const int32_t* part_index, c
     if (n <= 0) return;
     hipLaunchKernelGGL(k_window_starts, grid_of(n), 256, 0, s, part_flag, part_index, peer_flag, peer_index, n, part_start, peer_start);
     PA_HIP(hipGetLastError());
+}
+
+void launch_window_gather(int32_t type, const void* values, const uint8_t* nulls, const int32_t* perm, int32_t n, uint64_t* sorted_values,
+                          uint8_t* sorted_nulls, hipStream_t s)
+{
+    if (n <= 0 || (sorted_values == nullptr && sorted_nulls == nullptr)) return;
+    hipLaunchKernelGGL(k_window_gather, grid_of(n), 256, 0, s, type, values, nulls, perm, n, (u64*)sorted_values, sorted_nulls);
+    PA_HIP(hipGetLastError());
+}
+
+namespace {
+inline int64_t scan_tiles(int32_t n) { return ((int64_t)n + kWindowScanTile - 1) / kWindowScanTile; }
+
+template <int KIND>
+void launch_window_scan_of(int mode, const u64* values, const uint8_t* nulls, const int32_t* part_flag, int32_t n, void* out, int32_t* error, void* temp, hipStream_t s)
+{
+    const int tiles = (int)scan_tiles(n);
+    WindowAcc* tile_acc = static_cast<WindowAcc*>(temp);
+    WindowAcc* tile_front = tile_acc + tiles;
+    hipLaunchKernelGGL(k_window_scan_tiles<KIND>, tiles, 256, 0, s, values, nulls, part_flag, n, mode, tile_acc);
+    hipLaunchKernelGGL(k_window_scan_tile_fronts<KIND>, 1, 256, 0, s, (const WindowAcc*)tile_acc, (i32)tiles, mode, tile_front);
+    hipLaunchKernelGGL(k_window_scan_apply<KIND>, tiles, 256, 0, s, values, nulls, part_flag, n, mode, (const WindowAcc*)tile_front, out, error);
+    PA_HIP(hipGetLastError());
+}
+}  // namespace
+
+size_t window_scan_temp_bytes(int32_t n) { return (size_t)(2 * scan_tiles(n) + 1) * sizeof(WindowAcc); }
+
+void launch_window_scan(WindowScanKind kind, bool floating, const uint64_t* sorted_values, const uint8_t* sorted_nulls, const int32_t* part_flag,
+                        int32_t n, void* out, int32_t* error, void* temp, hipStream_t s)
+{
+    if (n <= 0) return;
+    const u64* v = (const u64*)sorted_values;
+    switch (kind) {
+        case kWindowScanCount: launch_window_scan_of<kWindowScanCount>(kCmpInt, v, sorted_nulls, part_flag, n, out, error, temp, s); break;
+        case kWindowScanSum: launch_window_scan_of<kWindowScanSum>(kCmpInt, v, sorted_nulls, part_flag, n, out, error, temp, s); break;
+        case kWindowScanMin: launch_window_scan_of<kWindowScanMin>(floating ? kCmpDoubleMin : kCmpInt, v, sorted_nulls, part_flag, n, out, error, temp, s); break;
+        case kWindowScanMax: launch_window_scan_of<kWindowScanMax>(floating ? kCmpDoubleMax : kCmpInt, v, sorted_nulls, part_flag, n, out, error, temp, s); break;
+    }
 }
 
 void launch_window_functions(const WindowFunctionArgs& a, hipStream_t s)

@@ -6,12 +6,19 @@
 //   scans     part_index / peer_index = exclusive scans of the flags (scan_kernels.hpp), so that the run of row i is
 //             index[i] + flag[i]: the flags up to and including its own.
 //   starts    the first row of run r stores its index in start[r]; row n - 1 also stores the sentinel n behind the last run.
+//   gather    (aggregates) per distinct argument channel: its values, widened to 8 bytes, and its NULL flags through perm into sorted
+//             order; one gather serves every function on the channel.
+//   agg scans (aggregates) per distinct (kind, channel): a segmented inclusive scan over sorted index that restarts where part_flag is
+//             set -- tile aggregates, the scan of the tile aggregates, apply: three launches, as scan_kernels.hip scans.
 //   functions per row: its partition p and peer group q, part_start[p], part_start[p + 1], peer_start[q], peer_start[q + 1] and the
-//             peer group of part_start[p]; every requested column written by sorted index.
+//             peer group of part_start[p]; every requested column written by sorted index.  An aggregate column reads the scanned state
+//             at the last row of its frame: part_start[p] + e, an index that never decreases with i.
 // Every array element has one writer per launch and no pass reads what the same launch writes: nothing is carried between workgroups
 // and nothing depends on the order in which waves run.  Algorithmic bytes per row: flags 4 (perm) + two random rows per channel,
 // scans 2 x (4 + 4), starts 16, functions 16 + 8 per column (+ 4 + the argument through perm for ntile); the start arrays are read at
-// indices that never decrease with i.
+// indices that never decrease with i.  Aggregates: gather 4 (perm) + a random value (and NULL byte) + 8 (+ 1) written; a scan reads its
+// input and part_flag twice (8 + 4 (+ 1) each time) and writes 8 (sum, min, max) or 4 (the non-null count); the function pass reads
+// 8 (+ 4 with NULLs) more per aggregate column.
 #pragma once
 
 #include "common.hpp"
@@ -20,6 +27,7 @@ namespace pa {
 
 constexpr int kWindowRowsPerBlock = 1024;   // rows of one workgroup of the function pass: 256 lanes x 4
 constexpr int kWindowMaxFunctions = 16;
+constexpr int kWindowScanTile = 1024;       // rows of one workgroup of the aggregate scans: 256 lanes x 4 consecutive rows
 
 // flag_a[i] = 1 (and flag_b[i] = 1 when flag_b is not null) for every 0 < i < n whose row perm[i] IS DISTINCT FROM row perm[i - 1] in
 // this channel: both NULL = equal; DOUBLE / REAL: any NaN equals any NaN, -0.0 equals +0.0; VARCHAR: length and bytes; BOOLEAN:
@@ -32,13 +40,39 @@ void launch_window_distinct(int32_t type, const void* values, const int32_t* off
 void launch_window_starts(const int32_t* part_flag, const int32_t* part_index, const int32_t* peer_flag, const int32_t* peer_index, int32_t n,
                           int32_t* part_start, int32_t* peer_start, hipStream_t s);
 
+// The argument channel of the aggregates in sorted order: sorted_values[i] = the value of row perm[i] as 8 bytes (BIGINT / short DECIMAL
+// as they are, INTEGER / DATE sign-extended, BOOLEAN 0 / 1, DOUBLE its bits, REAL widened to a double's bits: exact), sorted_nulls[i] =
+// its NULL flag.  Either output may be null (count reads the flags only; a channel without NULLs has none).
+void launch_window_gather(int32_t type, const void* values, const uint8_t* nulls, const int32_t* perm, int32_t n, uint64_t* sorted_values,
+                          uint8_t* sorted_nulls, hipStream_t s);
+
+// The segmented inclusive scans of the aggregates over sorted index, restarting where part_flag is set.  A NULL row (sorted_nulls, may
+// be null) leaves the state as it is.
+enum WindowScanKind {
+    kWindowScanCount = 0,   // out: int32 per row, the non-null rows of its partition up to and including it
+    kWindowScanSum = 1,     // out: int64 per row, the sum of those rows' values; a row whose sum leaves int64 ORs kWindowErrorSum into *error
+    kWindowScanMin = 2,     // out: 8 bytes per row, the first best of those rows' values (unspecified while there is none)
+    kWindowScanMax = 3
+};
+constexpr int32_t kWindowErrorBuckets = 1, kWindowErrorSum = 2;   // bits of the error word
+// bytes of `temp` for n rows: the tile aggregates and their exclusive scan
+size_t window_scan_temp_bytes(int32_t n);
+// floating: the values are doubles' bits (min in Double.compare order; max: NaN loses to everything, the zeros tie), else int64
+void launch_window_scan(WindowScanKind kind, bool floating, const uint64_t* sorted_values, const uint8_t* sorted_nulls, const int32_t* part_flag,
+                        int32_t n, void* out, int32_t* error, void* temp, hipStream_t s);
+
+enum WindowFrameEnd { kWindowFrameRow = 0, kWindowFramePeers = 1, kWindowFramePartition = 2 };   // e = i, pe - 1, N - 1
+
 struct WindowFunction {
     int32_t function;          // pa_window_function
-    int32_t arg_type;          // ntile: PA_BIGINT / PA_INTEGER
+    int32_t arg_type;          // ntile: PA_BIGINT / PA_INTEGER; min / max: the argument's type = the output's
     const void* arg_values;    // ntile: the argument channel by held row
     const uint8_t* arg_nulls;  // may be null
-    void* out;                 // n x 8 bytes by sorted index: BIGINT, or DOUBLE for percent_rank / cume_dist
-    uint8_t* out_nulls;        // ntile with arg_nulls: n bytes; else null
+    void* out;                 // by sorted index, n x 8 bytes: BIGINT, or DOUBLE for percent_rank / cume_dist; min / max: n x the type's width
+    uint8_t* out_nulls;        // ntile with arg_nulls, sum / min / max with `count`: n bytes; else null
+    int32_t frame_end;         // aggregates: WindowFrameEnd
+    const void* scan;          // sum / min / max: the scanned state by sorted index
+    const int32_t* count;      // count / sum / min / max: the scanned non-null count; null when the argument has no NULLs
 };
 struct WindowFunctionArgs {
     const int32_t* perm;       // sorted index -> held row (read for ntile only)
@@ -48,7 +82,7 @@ struct WindowFunctionArgs {
     const int32_t* peer_index;
     const int32_t* part_start;
     const int32_t* peer_start;
-    int32_t* error;            // set to 1 by a row whose ntile bucket count is <= 0
+    int32_t* error;            // a row whose ntile bucket count is <= 0 ORs kWindowErrorBuckets into it
     int32_t n;
     int32_t count;
     WindowFunction f[kWindowMaxFunctions];

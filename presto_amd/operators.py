@@ -993,6 +993,62 @@ def WindowOperator(input_types, output_channels, functions, partition_channels, 
                                  pre_sorted_channel_prefix, expected_positions, output_mem, stream, type_params).createOperator()
 
 
+DEFAULT_FRAME = (abi.FRAME_RANGE, abi.BOUND_UNBOUNDED_PRECEDING, abi.BOUND_CURRENT_ROW)   # what SQL means without a frame clause
+
+
+def FramedWindowOperatorFactory(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count=0,
+                                pre_sorted_channel_prefix=0, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """WindowOperatorFactory over pa_framed_window_desc: the ranking functions and count(*) / count / sum / min / max, each with its frame.
+    functions: an abi.WINDOW_* id, (id, [argument channels]) or (id, [argument channels], (frame_type, start_type, end_type)); a frame
+    may also be (frame_type, start_type, end_type, start_channel, end_channel, ignore_nulls).  No frame: DEFAULT_FRAME."""
+    d = abi.pa_framed_window_desc()
+    types = abi.int32_array(input_types)
+    oc = abi.int32_array(output_channels)
+    pc = abi.int32_array(partition_channels)
+    sc = abi.int32_array(sort_channels)
+    so = abi.int32_array(sort_orders)
+    functions = [(f, []) if isinstance(f, int) else tuple(f) for f in functions]
+    fs = (abi.pa_framed_window_function_desc * max(len(functions), 1))()
+    keep = [types, oc, pc, sc, so, fs]
+    for i, (function, arguments, *frame) in enumerate(functions):
+        args = abi.int32_array(arguments)
+        keep.append(args)
+        frame = tuple(frame[0]) if frame else DEFAULT_FRAME
+        frame = frame + (-1, -1, 0)[len(frame) - 3:]
+        fs[i].function = function
+        fs[i].argument_count = len(arguments)
+        fs[i].argument_channels = C.cast(args, C.POINTER(C.c_int32))
+        fs[i].frame_type, fs[i].start_type, fs[i].end_type, fs[i].start_channel, fs[i].end_channel, fs[i].ignore_nulls = frame
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.output_channel_count = len(output_channels)
+    d.output_channels = C.cast(oc, C.POINTER(C.c_int32))
+    d.function_count = len(functions)
+    d.functions = C.cast(fs, C.POINTER(abi.pa_framed_window_function_desc))
+    d.partition_channel_count = len(partition_channels)
+    d.partition_channels = C.cast(pc, C.POINTER(C.c_int32))
+    d.sort_channel_count = len(sort_channels)
+    d.sort_channels = C.cast(sc, C.POINTER(C.c_int32))
+    d.sort_orders = C.cast(so, C.POINTER(C.c_int32))
+    d.pre_grouped_channel_count = pre_grouped_channel_count
+    d.pre_sorted_channel_prefix = pre_sorted_channel_prefix
+    d.expected_positions = expected_positions
+    d.output_mem = output_mem
+    d.stream = stream
+    return OperatorFactory(lib().pa_framed_window_create, d, keep)
+
+
+def FramedWindowOperator(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count=0,
+                         pre_sorted_channel_prefix=0, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    return FramedWindowOperatorFactory(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count,
+                                       pre_sorted_channel_prefix, expected_positions, output_mem, stream, type_params).createOperator()
+
+
 # ---- driver loop ---------------------------------------------------------------------------------------
 def to_pages(operator, input_pages):
     """OperatorAssertion.toPages (core/trino-main/src/test/java/io/trino/operator/OperatorAssertion.java:62-138):
