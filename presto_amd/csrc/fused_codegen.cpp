@@ -253,6 +253,8 @@ void FusedGen::group_keys()
     }
     k.w = (int)packer.used.size();
     PA_REQUIRE(k.w <= 8, PA_ERR_NOT_SUPPORTED, "group key wider than 8 words");
+    // one word, at most 31 bits of it (NULL flags included): the few-groups tier keeps such keys as u32 (KernelInfo::packed_key)
+    k.packed_key = !brow && k.w == 1 && packer.used[0] <= 31;
 }
 
 int FusedGen::word(int kind, const std::string& cond, const std::string& val, const std::string& key)
@@ -418,7 +420,9 @@ void FusedGen::row_function(const std::string& name)
     for (int w = 0; w < k.nw; w++) {
         src << "bool u" << w << " = false; " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w << " = 0;\n";
     }
-    if (k.w > 0) src << "u64 key[PA_KW];\n#pragma unroll\nfor (int i = 0; i < PA_KW; i++) key[i] = 0;\n";
+    const bool key32 = variant == V_LDS && k.packed_key;  // (the few-groups tier's 32-bit key table: fused_tier_lds.cpp)
+    if (key32) src << "u32 key = 0u;\n";
+    else if (k.w > 0) src << "u64 key[PA_KW];\n#pragma unroll\nfor (int i = 0; i < PA_KW; i++) key[i] = 0;\n";
     src << "if (sel) {\n" << build_loads.str() << inner.str();
     for (int w = 0; w < k.nw; w++) src << "u" << w << " = " << words[w].cond << "; x" << w << " = " << words[w].val << ";\n";
     if (brow) {
@@ -426,9 +430,9 @@ void FusedGen::row_function(const std::string& name)
     }
     else {
         for (int i = 0; i < k.w; i++) {
-            src << "key[" << i << "] = ";
+            src << (key32 ? "key = (u32)(" : "key[" + std::to_string(i) + "] = ");
             for (size_t t = 0; t < word_terms[i].size(); t++) src << (t ? " | " : "") << word_terms[i][t];
-            src << ";\n";
+            src << (key32 ? ");\n" : ";\n");
         }
     }
     src << "}\n";
@@ -477,6 +481,7 @@ void FusedGen::emit_kernel(const std::string& name, int mode)
     if (mode == 3) {
         // (the loop above)
     }
+    else if (mode == 1 && k.packed_key && lds_pipe_level() > 0) lds_head_loop_ahead();
     else if (mode == 1) lds_head_loop();
     else if (mode == 2) lds_tail_loop();
     else if (variant == V_HASH) hash_tile_loop();

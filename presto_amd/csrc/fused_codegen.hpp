@@ -112,9 +112,12 @@ struct FusedGen {
     // ---- LDS (fused_tier_lds.cpp) ----
     void lds_check_capacity();
     void lds_declarations();
+    void lds_find_group();
+    void lds_find_group_packed();
     void lds_accumulate_row();
     void lds_kernel_begin();
     void lds_head_loop();
+    void lds_head_loop_ahead();
     void lds_tail_loop();
     void lds_kernel_end();
 

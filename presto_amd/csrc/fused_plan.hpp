@@ -153,6 +153,9 @@ struct KernelInfo {
     // the columns of stage 1 .. n - 1 into slab words gridDim.x * nw + blockIdx.x * (n - 1) + k - 1 (the decision: op_fused_kernels.cpp, staged_decide)
     std::vector<int> stage_bytes;
     int nw = 0, w = 0, c = 0, block = 256;
+    // the group key is "packed": one key word, of which the parts and their NULL flags use at most 31 bits.  The few-groups tier
+    // then keeps its key table as 32-bit words whose empty value, 0xFFFFFFFF, no key can take (fused_tier_lds.cpp)
+    bool packed_key = false;
     int lc = 0;  // V_LDSH: slots of the workgroup's LDS table
     // V_BROW: the accumulator word every row of a group updates -- "this build row has a group" is read off it (its value differs
     // from occ_empty), and the kernel stores no tags -- or -1: tags are stored
@@ -188,6 +191,10 @@ void plan_stages(Spec& s);
 int range_entry_words(const Spec& s, const std::vector<ChannelLayout>& layout);
 // the translation unit of one tier (`variant`) for pages of one layout signature (fused_codegen.cpp)
 KernelInfo generate(const Spec& s, const std::vector<ChannelLayout>& layout, int variant);
+// PRESTO_AMD_LDS_PIPE (measurement switch, default 1): 0 = the few-groups tier's head loop over a packed key loads a quad and works on
+// it, instead of loading the next quad first.  The switch changes the generated source, hence the kernel's name; an operator's plan
+// fingerprint carries it, so that kernels generated under another setting are not shared.
+int lds_pipe_level();
 
 }  // namespace fused
 }  // namespace pa

@@ -50,42 +50,70 @@ void emit_prologue(const RowInputs& s, const std::vector<ChannelLayout>& layout,
 // speculatively at the position they have when every earlier string of the page is one byte long, and
 // fall back to the offset-dependent path otherwise.  Under U<c> (emit_prologue) the quad's offsets are those positions unless one of
 // its bytes is not ASCII: they are computed, not loaded -- after the independent loads, since the choice waits for the key bytes.
-void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, std::string args[4], const ColumnNames& nm)
+// With `ahead` the independent loads are listed instead of written (QuadLoad): the caller issues them a quad early and `o` receives
+// the rest, which is then the same text but for the waits that end the rarely taken arms (see `drain`).
+std::string QuadLoad::into(const std::string& dst, const std::string& q) const
+{
+    std::string out;
+    for (size_t i = 0; i < stmt.size(); i++) {
+        if (stmt[i] == '@' && i + 1 < stmt.size() && (stmt[i + 1] == 'd' || stmt[i + 1] == 'q')) out += stmt[++i] == 'd' ? dst : "(" + q + ")";
+        else out += stmt[i];
+    }
+    return out;
+}
+
+void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, std::string args[4], const ColumnNames& nm,
+                       std::vector<QuadLoad>* ahead)
 {
     static const char* xyzw[4] = {"x", "y", "z", "w"};
     std::ostringstream mid, post;
+    // (the loads of a 16-byte type: two halves of the quad as A<c>, B<c>, or the whole quad as A<c>)
+    // With a quad's loads in flight behind it, an arm that few quads take waits for its own loads before it ends: vmcnt counts loads
+    // in the order of their issue, and a wait for such a load placed behind the arm -- where the compiler puts it, at the first use --
+    // is a wait for everything issued before it, in every quad.  (0x0F70: s_waitcnt vmcnt(0) alone.)
+    const std::string drain = ahead ? " __builtin_amdgcn_s_waitcnt(0x0F70);" : "";
+    auto halves = [&](const std::string& type, const std::string& C, const std::string& V) {
+        ahead->push_back({type, "A" + C, "@d = ((const " + type + "*)" + V + ")[2 * @q];"});
+        ahead->push_back({type, "B" + C, "@d = ((const " + type + "*)" + V + ")[2 * @q + 1];"});
+    };
     for (int c = 0; c < s.n_in; c++) {
         if (!s.used[c]) continue;
         const std::string C = std::to_string(c), V = nm.v(c), O = nm.o(c), NL = nm.nl(c);
         switch (layout[c].type) {
             case PA_BIGINT:
             case PA_DECIMAL:  // ShortDecimalType: a LongArrayBlock of unscaled values
-                o << "        pa_i64x2 A" << C << " = ((const pa_i64x2*)" << V << ")[2 * q], B" << C << " = ((const pa_i64x2*)" << V
-                  << ")[2 * q + 1];\n";
+                if (ahead) halves("pa_i64x2", C, V);
+                else o << "        pa_i64x2 A" << C << " = ((const pa_i64x2*)" << V << ")[2 * q], B" << C << " = ((const pa_i64x2*)" << V
+                       << ")[2 * q + 1];\n";
                 for (int r = 0; r < 4; r++) args[r] += ", " + std::string(r < 2 ? "A" : "B") + C + "." + xyzw[r & 1];
                 break;
             case PA_LONG_DECIMAL:  // 16 bytes per position: one 16-byte load per row
                 for (int r = 0; r < 4; r++) {
-                    o << "        pa_i64x2 L" << C << r << " = ((const pa_i64x2*)" << V << ")[4 * q + " << r << "];\n";
+                    if (ahead) ahead->push_back({"pa_i64x2", "L" + C + std::to_string(r), "@d = ((const pa_i64x2*)" + V + ")[4 * @q + " + std::to_string(r) + "];"});
+                    else o << "        pa_i64x2 L" << C << r << " = ((const pa_i64x2*)" << V << ")[4 * q + " << r << "];\n";
                     args[r] += ", pa_ld_from(L" + C + std::to_string(r) + ".x, L" + C + std::to_string(r) + ".y)";
                 }
                 break;
             case PA_DOUBLE:
-                o << "        pa_f64x2 A" << C << " = ((const pa_f64x2*)" << V << ")[2 * q], B" << C << " = ((const pa_f64x2*)" << V
-                  << ")[2 * q + 1];\n";
+                if (ahead) halves("pa_f64x2", C, V);
+                else o << "        pa_f64x2 A" << C << " = ((const pa_f64x2*)" << V << ")[2 * q], B" << C << " = ((const pa_f64x2*)" << V
+                       << ")[2 * q + 1];\n";
                 for (int r = 0; r < 4; r++) args[r] += ", " + std::string(r < 2 ? "A" : "B") + C + "." + xyzw[r & 1];
                 break;
             case PA_INTEGER:
             case PA_DATE:
-                o << "        pa_i32x4 A" << C << " = ((const pa_i32x4*)" << V << ")[q];\n";
+                if (ahead) ahead->push_back({"pa_i32x4", "A" + C, "@d = ((const pa_i32x4*)" + V + ")[@q];"});
+                else o << "        pa_i32x4 A" << C << " = ((const pa_i32x4*)" << V << ")[q];\n";
                 for (int r = 0; r < 4; r++) args[r] += ", (i64)A" + C + "." + xyzw[r];
                 break;
             case PA_REAL:
-                o << "        pa_f32x4 A" << C << " = ((const pa_f32x4*)" << V << ")[q];\n";
+                if (ahead) ahead->push_back({"pa_f32x4", "A" + C, "@d = ((const pa_f32x4*)" + V + ")[@q];"});
+                else o << "        pa_f32x4 A" << C << " = ((const pa_f32x4*)" << V << ")[q];\n";
                 for (int r = 0; r < 4; r++) args[r] += ", A" + C + "." + xyzw[r];
                 break;
             case PA_BOOLEAN:
-                o << "        u32 A" << C << " = ((const u32*)" << V << ")[q];\n";
+                if (ahead) ahead->push_back({"u32", "A" + C, "@d = ((const u32*)" + V + ")[@q];"});
+                else o << "        u32 A" << C << " = ((const u32*)" << V << ")[q];\n";
                 for (int r = 0; r < 4; r++) args[r] += ", ((A" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
                 break;
             case PA_VARCHAR: {
@@ -93,7 +121,11 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
                 if (s.short_bound[c] == 1) {
                     mid << "        pa_i32x4 O" << C << "; i32 E" << C << ";\n        if (U" << C << " && (K" << C << " & 0x80808080u) == 0u) {\n"
                         << "            const i32 b = P" << C << " + (i32)(4 * q);\n            O" << C << ".x = b; O" << C << ".y = b + 1; O" << C
-                        << ".z = b + 2; O" << C << ".w = b + 3; E" << C << " = b + 4;\n        } else {\n            " << load_offsets << "\n        }\n";
+                        << ".z = b + 2; O" << C << ".w = b + 3; E" << C << " = b + 4;\n        } else {\n            " << load_offsets << drain << "\n        }\n";
+                }
+                else if (ahead) {
+                    ahead->push_back({"pa_i32x4", "O" + C, "@d = ((const pa_i32x4*)" + O + ")[@q];"});
+                    ahead->push_back({"i32", "E" + C, "@d = " + O + "[4 * @q + 4];"});
                 }
                 else {
                     o << "        pa_i32x4 O" << C << " = ((const pa_i32x4*)" << O << ")[q]; i32 E" << C << " = " << O << "[4 * q + 4];\n";
@@ -106,11 +138,12 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
                 if (s.short_bound[c] > 0) {
                     post << "        u64 S" << C << "0, S" << C << "1, S" << C << "2, S" << C << "3;\n";
                     if (s.short_bound[c] == 1) {
-                        o << "        u32 K" << C << " = 0u; if (4 * q + 4 <= PB" << C << ") __builtin_memcpy(&K" << C << ", (const u8*)" << V
-                          << " + P" << C << " + 4 * q, 4);\n";
+                        if (ahead) ahead->push_back({"u32", "K" + C, "@d = 0u; if (4 * @q + 4 <= PB" + C + ") __builtin_memcpy(&@d, (const u8*)" + V + " + P" + C + " + 4 * @q, 4);"});
+                        else o << "        u32 K" << C << " = 0u; if (4 * q + 4 <= PB" << C << ") __builtin_memcpy(&K" << C << ", (const u8*)" << V
+                               << " + P" << C << " + 4 * q, 4);\n";
                         post << "        if (E" << C << " - " << lo[0] << " == 4) {\n            u32 pk = K" << C << ";\n            if (" << lo[0]
-                             << " != P" << C << " + (i32)(4 * q) || 4 * q + 4 > PB" << C << ") __builtin_memcpy(&pk, (const u8*)" << V << " + "
-                             << lo[0] << ", 4);\n";
+                             << " != P" << C << " + (i32)(4 * q) || 4 * q + 4 > PB" << C << ") " << (ahead ? "{ " : "") << "__builtin_memcpy(&pk, (const u8*)" << V
+                             << " + " << lo[0] << ", 4);" << (ahead ? drain + " }" : "") << "\n";
                         for (int r = 0; r < 4; r++) post << "            S" << C << r << " = (pk >> " << 8 * r << ") & 0xffu;\n";
                         post << "        } else {\n";
                     }
@@ -121,6 +154,7 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
                         post << "            S" << C << r << " = pa_short_bytes((const u8*)" << V << " + " << lo[r] << ", " << len[r] << ", "
                              << s.short_bound[c] << ", a.err);\n";
                     }
+                    if (ahead && s.short_bound[c] == 1) post << "           " << drain << "\n";
                     post << "        }\n";
                 }
                 for (int r = 0; r < 4; r++) {
@@ -134,7 +168,8 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
         }
         if (layout[c].nullable) {
             // a page without a valueIsNull array on a channel that had one earlier passes a null pointer
-            o << "        u32 N" << C << " = " << NL << " ? ((const u32*)" << NL << ")[q] : 0u;\n";
+            if (ahead) ahead->push_back({"u32", "N" + C, "@d = " + NL + " ? ((const u32*)" + NL + ")[@q] : 0u;"});
+            else o << "        u32 N" << C << " = " << NL << " ? ((const u32*)" << NL << ")[q] : 0u;\n";
             for (int r = 0; r < 4; r++) args[r] += ", ((N" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";
         }
     }

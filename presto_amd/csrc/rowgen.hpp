@@ -30,9 +30,17 @@ std::string row_params(const RowInputs& s, const std::vector<ChannelLayout>& lay
 std::string row_param_names(const RowInputs& s, const std::vector<ChannelLayout>& layout);
 // wave-uniform per-page values the vector loads rely on (emit once, before the loops)
 void emit_prologue(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, const ColumnNames& names = ColumnNames());
-// vector loads of row quad q (into `o`) and the 4 argument lists of the per-row calls
+// One independent load of a row quad -- a load whose address follows from the quad's number alone -- as a variable: its type and name
+// and the statement that loads it, with @d for the variable written and @q for the quad (QuadLoad::into).
+struct QuadLoad {
+    std::string type, name, stmt;
+    std::string into(const std::string& dst, const std::string& q) const;
+};
+// vector loads of row quad q (into `o`) and the 4 argument lists of the per-row calls.  With `ahead` the independent loads are not
+// written but listed there, for a loop that issues them one quad early and hands them over under their names; `o` then receives
+// only what follows them (the offsets of a VARCHAR(1) quad that needs them, the packed bytes of short keys).
 void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::ostringstream& o, std::string args[4],
-                       const ColumnNames& names = ColumnNames());
+                       const ColumnNames& names = ColumnNames(), std::vector<QuadLoad>* ahead = nullptr);
 // The vector loads of a quad as a list of variables (type, name, the load of quad `q` as an expression) and the argument lists over
 // variables named <prefix><name>, for loops that keep several quads in flight (the next one being loaded, the current one, the one
 // whose rows are still to be accumulated).  false: some used channel does not load that simply (VARCHAR, long DECIMAL).
