@@ -137,6 +137,7 @@ private:
         std::string sig;
         std::vector<ChannelLayout> layout;
         uint64_t seq = 0;     // position among the operator's few-groups launches (release_checkpoint)
+        bool late_ctl = false;  // its control block is copied behind its merge, on the merge stream: lds_.ev_merge[b] confirms it
     };
     // the pending range of stable device pages that continue each other in memory
     struct Run {
@@ -308,8 +309,24 @@ private:
     int ranked_channel(int proj) const;
 
     // ==== the result page (op_fused_output.cpp) ==========================================================================
-    void build_output();
+    void build_output(bool eager = false);
+    bool fetch_result(const KernelInfo& ki, std::vector<uint64_t>& keys, std::vector<uint64_t>& words, int64_t& groups);
+    void assemble_output(const KernelInfo& ki, const std::vector<uint64_t>& keys, const std::vector<uint64_t>& words, int64_t groups);
     bool emit_on_device(const KernelInfo& ki, int64_t groups, bool keys_from_build_columns = false);
+    // ---- the eager result: finish() enqueues, behind the operator's last launch, everything get_output needs of a small result -- the
+    // control block, the ungrouped state or the compacted rows of at most kEagerGroups groups -- into pinned memory and records
+    // eager_.event.  get_output waits for that event alone (never for the stream, which other operators share), validates what
+    // landed (eager_result_holds) and assembles the page from it; a result that does not hold is dropped and fetch_result runs.
+    // PRESTO_AMD_EAGER_OUTPUT=0 (read when the operator is made): nothing is enqueued at finish.
+    // kEagerGroups stays below emit_on_device's threshold: a result is either eager or emitted on the device, never a choice.
+    static constexpr int64_t kEagerGroups = 1024;
+    static constexpr uint32_t kEagerTableSlots = 1u << 20;  // a larger table's scan is not spent on a guess
+    bool eager_possible() const;
+    void enqueue_eager_result();
+    bool eager_result_holds();
+    void take_eager_result(std::vector<uint64_t>& keys, std::vector<uint64_t>& words, int64_t& groups) const;
+    // ---- the operator's own last work on the main stream: what the destructor waits for instead of the whole (shared) stream ----
+    void mark_last_event();
 
     // ==== data members, by owner ==========================================================================================
     // Pooled buffers return to their caches in the members' destructors, after ~FusedAggregationOperator has drained the streams;
@@ -426,6 +443,24 @@ private:
     PageStager dict_stager_;
     std::vector<DevBuf> dict_key_bufs_;  // per interned channel: uploaded ids, key ids, key NULL flags of a dictionary page
     std::vector<std::unique_ptr<RankedChannel>> ranked_;
+
+    // ---- the eager result and the operator's last event (op_fused_output.cpp) ----
+    struct Eager {
+        bool on = true;          // PRESTO_AMD_EAGER_OUTPUT
+        bool queued = false;     // finish() has enqueued the result; event, recorded behind it, says when it has landed
+        hipEvent_t event = nullptr;
+        bool with_state = false;  // the ungrouped state was copied behind the control block
+        size_t rows = 0;         // ... or this many dense rows of keys, then of words (0: the table did not exist)
+        uint64_t begun = 0;      // timer.begun() at finish: a launch after it (a redo at confirmation) voids the result
+        PinnedBuf land;          // [0..31] control block, then the state words, or kEagerGroups rows of keys and of words
+    } eager_;
+    // Recorded on the main stream behind everything the operator has enqueued there, by every path that enqueues after the last
+    // add_input (finish -- again behind an eager result that went to the main stream --, get_output's legacy path, emit_states);
+    // last_valid_ is false from the first enqueue until it is recorded, and again after a redo at confirmation.  The destructor waits for it -- and, through pool_stream_release, for the merge stream, the eager result's copies on it
+    // included -- before the members' destructors hand the pooled buffers back: that wait is what keeps a buffer out of the pool
+    // while this operator's work still uses it.
+    hipEvent_t last_event_ = nullptr;
+    bool last_valid_ = false;  // (the constructor already enqueues: the control block's memset)
 
     // ---- the result page (op_fused_output.cpp) ----
     PinnedBuf h_table_, h_parts_;

@@ -264,6 +264,8 @@ bool FusedAggregationOperator::launch_global(const Compiled& ck, const DevPage& 
     timer.begin(s);
     PA_HIP(hipModuleLaunchKernel(ck.kernel.fn, grid, 1, 1, ki.block, 1, 1, 0, s, params, nullptr));
     timer.end(s, true);
+    // (on the main stream: moved to a second stream behind an event, as the few-groups tier's merges are, the 8 us kernel left the
+    // gap between two launches what the timer's and the event's markers make it -- 39 instead of 43 us per Q6 pass)
     launch_merge_global_slab(a.slab, grid, ki.nw, ck.kinds.as<int32_t>(), state_.as<uint64_t>(), ctl_, s);
     if (!ki.stage_bytes.empty()) staged_decide(ck, a.slab, grid, a.vec ? (n & ~(int64_t)3) : 0, s);
     return true;
@@ -329,14 +331,19 @@ bool FusedAggregationOperator::launch_lds(const Compiled& ck, const DevPage& dp,
         PA_HIP(hipModuleLaunchKernel(use_tail ? ck.tail_kernel.fn : ck.kernel.fn, grid, 1, 1, ki.block, 1, 1, 0, s, params, nullptr));
         timer.end(s, !use_tail);
         // The merge skips itself when the launch overflowed (overflow_rows != 0).  It runs on the merge
-        // stream, overlapped with the next page's fused kernel; the host only waits for the fused kernel
-        // and the control block (error word, group count, overflow counters).
-        PA_HIP(hipMemcpyAsync(h_ctl_lds(b), ctl_, 32, hipMemcpyDeviceToHost, s));
+        // stream, overlapped with the next page's fused kernel.  The control block (error word, group count, overflow
+        // counters) is copied for the host behind the merge, on that stream too, when the launch is confirmed late anyway:
+        // the main stream then carries nothing between two pages' fused kernels.  A launch the host waits for at once -- the
+        // first of all, or one over a page that cannot be read again -- keeps its copy behind the kernel: the wait is for
+        // the kernel alone.
+        const bool late_ctl = lds_.probed && retained_;
+        if (!late_ctl) PA_HIP(hipMemcpyAsync(h_ctl_lds(b), ctl_, 32, hipMemcpyDeviceToHost, s));
         PA_HIP(hipEventRecord(lds_.ev_main[b], s));
         PA_HIP(hipStreamWaitEvent(lds_.merge_stream, lds_.ev_main[b], 0));
         launch_merge_lds_slab(a.slab, grid, ki.c, ki.w, ki.nw, ck.kinds.as<int32_t>(), a.gt_tag, a.gt_keys, a.gt_words, a.gt_mask,
                               a.gt_max_fill, a.gt_count, ctl_, a.overflow_rows,
                               static_cast<int32_t*>(lds_.entry_slot[b].ensure((size_t)grid * ki.c * 4)), lds_.merge_stream);
+        if (late_ctl) PA_HIP(hipMemcpyAsync(h_ctl_lds(b), ctl_, 32, hipMemcpyDeviceToHost, lds_.merge_stream));
         PA_HIP(hipEventRecord(lds_.ev_merge[b], lds_.merge_stream));
         lds_.merge_pending[b] = true;
         lds_.page++;
@@ -353,6 +360,7 @@ bool FusedAggregationOperator::launch_lds(const Compiled& ck, const DevPage& dp,
         f.sig = *cur_sig_;
         f.layout = *cur_layout_;
         f.seq = ++lds_.launch_seq;
+        f.late_ctl = late_ctl;
         lds_.inflight.push_back(std::move(f));
         if (!lds_.probed) {
             // the first launch of all: when it gives up, its rows are not redone on their own -- the page goes to the next
@@ -575,7 +583,11 @@ bool FusedAggregationOperator::launch_table(const Compiled& ck, const DevPage& d
 // confirms the launches whose kernel has finished, without waiting
 void FusedAggregationOperator::poll_inflight()
 {
-    while (!lds_.inflight.empty() && hipEventQuery(lds_.ev_main[lds_.inflight.front().b]) == hipSuccess) confirm_oldest();
+    while (!lds_.inflight.empty()) {
+        const Inflight& f = lds_.inflight.front();
+        if (hipEventQuery(f.late_ctl ? lds_.ev_merge[f.b] : lds_.ev_main[f.b]) != hipSuccess) break;
+        confirm_oldest();
+    }
     (void)hipGetLastError();  // hipErrorNotReady is not an error here
 }
 
@@ -594,7 +606,12 @@ bool FusedAggregationOperator::confirm_oldest(bool redo)
 {
     Inflight f = std::move(lds_.inflight.front());
     lds_.inflight.pop_front();
-    PA_HIP(hipEventSynchronize(lds_.ev_main[f.b]));
+    // The launch's control block as it was behind its kernel (ev_main) or, late_ctl, behind its merge (ev_merge).  Either copy
+    // tells the same about the launch: its overflow word is written by the fused kernel alone -- the merge only reads it, to skip
+    // itself -- and a later launch has a word of its own until this one is confirmed.  The group count differs: behind the merge it
+    // includes this launch's groups, so groups_upper is exact for every confirmed launch and only the unconfirmed ones (at most
+    // kMaxInflight, counting the launch about to be made) add their grid * C each -- what launch_lds sizes the table for.
+    PA_HIP(hipEventSynchronize(f.late_ctl ? lds_.ev_merge[f.b] : lds_.ev_main[f.b]));
     const int32_t* hc = h_ctl_lds(f.b);
     uint64_t overflow;
     memcpy(&overflow, hc + 2 + 2 * f.b, 8);
@@ -609,6 +626,7 @@ bool FusedAggregationOperator::confirm_oldest(bool redo)
     // more groups than the wave's register table: the launch's merge skipped itself; its rows -- and every later page --
     // go to the workgroup-level LDS table, which itself hands rows it has no room for to the HBM table
     hipStream_t s = stream_.get();
+    last_valid_ = false;  // (the redo goes to the stream behind whatever finish() recorded)
     drain_merges();
     PA_HIP(hipMemsetAsync(ctl_ + 2 + 2 * f.b, 0, 8, s));
     if (mode_ == V_LDS) mode_ = V_LDSH;

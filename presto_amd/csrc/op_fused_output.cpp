@@ -185,11 +185,10 @@ bool FusedAggregationOperator::emit_on_device(const KernelInfo& ki, int64_t grou
 // AggregationOperator.getOutput (…/AggregationOperator.java:164-186) with the output functions of SURVEY a15.
 // Group counts here are tiny next to the input (Q1: 4 rows), so the states are brought to the host and the
 // output blocks assembled there; column order = keys, ($hashvalue), aggregates.
-void FusedAggregationOperator::build_output()
+void FusedAggregationOperator::build_output(bool eager)
 {
     HostTraceScope trace("  fused.build_output");
-    hipStream_t s = stream_.get();
-    drain_merges();
+    if (!eager) drain_merges();
     // any signature works for the layout (all share nw_/w_): take the first compiled kernel, or build
     // one for the all-non-null layout when no page ever arrived
     if (compiled_.empty()) {
@@ -202,8 +201,18 @@ void FusedAggregationOperator::build_output()
         compiled_["-"] = std::move(c);
     }
     const KernelInfo& ki = compiled_.begin()->second->info;
+    std::vector<uint64_t> keys, words;
+    int64_t groups = 0;
+    if (eager) take_eager_result(keys, words, groups);
+    else if (!fetch_result(ki, keys, words, groups)) return;
+    assemble_output(ki, keys, words, groups);
+}
 
-    // the error word and, for grouped results, the dense (keys, words) rows of the occupied table slots
+// The result from the device, one round trip per piece: the error word and, for grouped results, the dense (keys, words) rows of the
+// occupied table slots.  false: the output blocks were written on the device (emit_on_device), nothing is left to assemble.
+bool FusedAggregationOperator::fetch_result(const KernelInfo& ki, std::vector<uint64_t>& keys, std::vector<uint64_t>& words, int64_t& groups)
+{
+    hipStream_t s = stream_.get();
     const bool sub_tables = grouped_ && ldsp_.parts > 0;
     const int32_t* per_part = nullptr;
     if (sub_tables) {
@@ -248,8 +257,6 @@ void FusedAggregationOperator::build_output()
         }
         ldsp_.parts = 0;
     }
-    std::vector<uint64_t> keys, words;
-    int64_t groups = 0;
     if (!grouped_) {
         groups = 1;
         words.assign(nw_, 0);
@@ -265,7 +272,7 @@ void FusedAggregationOperator::build_output()
             raise_if(h_ctl_[0]);
         }
         // build-row table of some size: the output blocks straight from the accumulators and the build columns
-        if (build_rows_table_ && (int64_t)gt_.cap >= (1 << 14) && emit_on_device(ki, (int64_t)gt_.cap, true)) return;
+        if (build_rows_table_ && (int64_t)gt_.cap >= (1 << 14) && emit_on_device(ki, (int64_t)gt_.cap, true)) return false;
         if (build_rows_table_) {
             // build-row table: no kernel counted its groups, and its key words are still to be written -- once per group, from
             // the build columns (pa_brow_keys)
@@ -287,7 +294,7 @@ void FusedAggregationOperator::build_output()
             raise_if(h_ctl_[0]);
         }
         groups = h_ctl_[1];
-        if (emit_on_device(ki, groups)) return;
+        if (emit_on_device(ki, groups)) return false;
         if (groups > 0) {
             const int kw = std::max(w_, 1);
             dense_keys_.ensure((size_t)groups * kw * 8);
@@ -309,6 +316,13 @@ void FusedAggregationOperator::build_output()
             words.assign(hw, hw + (size_t)groups * nw_);
         }
     }
+    return true;
+}
+
+// The output blocks of `groups` groups from their key and accumulator words, assembled on the host.
+void FusedAggregationOperator::assemble_output(const KernelInfo& ki, const std::vector<uint64_t>& keys, const std::vector<uint64_t>& words, int64_t groups)
+{
+    hipStream_t s = stream_.get();
     PA_REQUIRE(groups <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "too many groups for one output page");
     out_rows_ = (int32_t)groups;
 
@@ -679,6 +693,101 @@ void FusedAggregationOperator::build_output()
         }
     }
     if (to_device) PA_HIP(hipStreamSynchronize(s));
+}
+
+// ---- the eager result (see op_fused.hpp) ---------------------------------------------------------------------------------------
+
+// One test decides at finish() whether the result is enqueued: everything whose legacy path does more than "control block, then the
+// state or the compacted rows" stays out -- generations and their combiner, partition-owned tables and replicas (both are folded
+// first), build-row tables (their keys are still to be written), a TopN hint, device output memory, keys whose dictionary must be
+// fetched, min / max by rank.  Grouped: the groups known to the host are a lower bound of what the table holds, so more than
+// kEagerGroups of them already rule the result out.
+bool FusedAggregationOperator::eager_possible() const
+{
+    if (!eager_.on || next_ || is_combiner_ || parked_) return false;
+    if (ldsp_.parts > 0 || gt_.rep > 1 || build_rows_table_ || topn_hint_.n > 0) return false;
+    if (spec_.output_mem == PA_MEM_DEVICE || spec_.any_ranked()) return false;
+    for (int c = 0; c < spec_.n_in; c++) {
+        if (spec_.interned[c]) return false;
+    }
+    return !grouped_ || (gt_.cap <= kEagerTableSlots && gt_.groups_upper <= (uint64_t)kEagerGroups);
+}
+
+// Where the operator has a second stream, the result is enqueued THERE: behind the merges it reads (one stream, in order) and behind
+// last_event_, which finish() has just recorded on the main stream (whatever the main stream itself wrote to the table: the table
+// tiers, a redo).  The main stream -- and the kernels of the operator that follows on it -- then never waits for this operator's
+// last merge; measured, with the result on the main stream Q6's first kernel started 80 us later behind Q1.
+void FusedAggregationOperator::enqueue_eager_result()
+{
+    hipStream_t s = stream_.get();
+    if (lds_.merge_stream) {
+        s = lds_.merge_stream;
+        PA_HIP(hipStreamWaitEvent(s, last_event_, 0));
+    }
+    if (!eager_.event) PA_HIP(hipEventCreateWithFlags(&eager_.event, hipEventDisableTiming));
+    const size_t kw = (size_t)std::max(w_, 1), nw = (size_t)nw_;
+    eager_.with_state = !grouped_ && state_.ptr() != nullptr;
+    eager_.rows = grouped_ && gt_.cap > 0 ? (size_t)std::min<int64_t>(kEagerGroups, (int64_t)gt_.cap) : 0;
+    uint8_t* land = static_cast<uint8_t*>(eager_.land.ensure(32 + (grouped_ ? eager_.rows * (kw + nw) : nw) * 8));
+    if (eager_.rows > 0) {
+        // the host does not know the group count here: the dense buffers have room for every slot of the table, and only the first
+        // kEagerGroups rows travel -- eager_result_holds looks at the count that comes with them
+        dense_keys_.ensure((size_t)gt_.cap * kw * 8);
+        dense_words_.ensure(std::max<size_t>((size_t)gt_.cap * nw * 8, 8));
+        PA_HIP(hipMemsetAsync(ctl_ + 7, 0, 4, s));
+        const GtStrides st = table_strides();
+        launch_gt_compact(table_tags(), gt_.keys.as<uint64_t>(), table_words(), gt_.cap, (int)kw, nw_, dense_keys_.as<uint64_t>(),
+                          dense_words_.as<uint64_t>(), reinterpret_cast<uint32_t*>(ctl_ + 7), s, &st);
+    }
+    PA_HIP(hipMemcpyAsync(land, ctl_, 32, hipMemcpyDeviceToHost, s));
+    if (eager_.with_state && nw > 0) PA_HIP(hipMemcpyAsync(land + 32, state_.ptr(), nw * 8, hipMemcpyDeviceToHost, s));
+    if (eager_.rows > 0) {
+        PA_HIP(hipMemcpyAsync(land + 32, dense_keys_.ptr(), eager_.rows * kw * 8, hipMemcpyDeviceToHost, s));
+        if (nw > 0) PA_HIP(hipMemcpyAsync(land + 32 + eager_.rows * kw * 8, dense_words_.ptr(), eager_.rows * nw * 8, hipMemcpyDeviceToHost, s));
+    }
+    PA_HIP(hipEventRecord(eager_.event, s));
+    if (s == stream_.get()) mark_last_event();  // (the copies are the operator's last work on the main stream now)
+    eager_.begun = timer.begun();
+    eager_.queued = true;
+}
+
+// get_output's one wait, and the validation of what finish() enqueued on a guess.  false: there is no eager result, or it does not
+// hold -- a launch confirmed only now had overflowed and its rows were redone behind the copies, or the table held more groups than
+// rows were copied -- and the legacy path runs as if nothing had been enqueued.
+bool FusedAggregationOperator::eager_result_holds()
+{
+    if (!eager_.queued) return false;
+    eager_.queued = false;
+    PA_HIP(hipEventSynchronize(eager_.event));
+    confirm_all();
+    if (timer.begun() != eager_.begun || next_) return false;
+    const int32_t* ctl = eager_.land.as<int32_t>();
+    raise_if(ctl[0]);
+    if (!grouped_) return true;
+    const int64_t groups = ctl[1];
+    if (groups == 0) return true;
+    return groups <= (int64_t)eager_.rows && (int64_t)(uint32_t)ctl[7] == groups;
+}
+
+void FusedAggregationOperator::take_eager_result(std::vector<uint64_t>& keys, std::vector<uint64_t>& words, int64_t& groups) const
+{
+    const uint8_t* land = eager_.land.as<uint8_t>();
+    if (!grouped_) {
+        groups = 1;
+        words.assign(nw_, 0);
+        if (eager_.with_state && nw_ > 0) memcpy(words.data(), land + 32, (size_t)nw_ * 8);
+        return;
+    }
+    groups = reinterpret_cast<const int32_t*>(land)[1];
+    if (groups == 0) return;
+    const int kw = std::max(w_, 1);
+    const uint64_t* hk = reinterpret_cast<const uint64_t*>(land + 32);
+    const uint64_t* hw = hk + eager_.rows * (size_t)kw;
+    keys.resize((size_t)groups * w_);
+    for (int64_t g = 0; g < groups; g++) {
+        for (int w = 0; w < w_; w++) keys[(size_t)g * w_ + w] = hk[(size_t)g * kw + w];
+    }
+    words.assign(hw, hw + (size_t)groups * nw_);
 }
 
 }  // namespace fused_op
