@@ -549,8 +549,9 @@ typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingTy
  * BY k ... ORDER BY x ...)`, planned by LocalExecutionPlanner.visitWindow (WindowOperator.java over RegularWindowPartition and the
  * functions of operator/window/).  These six ignore frames.  Value functions (lag, lead, first_value, last_value, nth_value), aggregate
  * window functions, frames, pre-grouped / pre-sorted input, spill and pattern recognition have no id here: the caller keeps the
- * reference operator for a window node that uses one.  count / sum / min / max over the frames that start at UNBOUNDED PRECEDING live
- * in the framed form of this descriptor, pa_framed_window_desc below (pa_framed_window_create); ids above 5 stay unknown here.
+ * reference operator for a window node that uses one.  count / sum / min / max and the value functions over the frames that start at
+ * UNBOUNDED PRECEDING live in the framed form of this descriptor, pa_framed_window_desc below (pa_framed_window_create); ids above 5
+ * stay unknown here.
  *   Order: the rows are sorted by SimplePageWithPositionComparator over [partition channels, each ASC_NULLS_LAST] + [sort channels with
  *     their orders] (WindowOperator.java:294), under the rules of pa_order_by_desc.  Rows that compare equal on all of those channels
  *     stay in arrival order (the reference's sort leaves this open; it is what TopN, OrderBy and TopNRanking promise here too).
@@ -590,7 +591,9 @@ typedef struct pa_topn_ranking_desc {    /* TopNRankingOperatorFactory(rankingTy
 typedef enum pa_window_function {
     PA_WINDOW_ROW_NUMBER = 0, PA_WINDOW_RANK = 1, PA_WINDOW_DENSE_RANK = 2, PA_WINDOW_PERCENT_RANK = 3, PA_WINDOW_CUME_DIST = 4, PA_WINDOW_NTILE = 5,
     /* the aggregates: pa_framed_window_desc only */
-    PA_WINDOW_COUNT_STAR = 6, PA_WINDOW_COUNT = 7, PA_WINDOW_SUM = 8, PA_WINDOW_MIN = 9, PA_WINDOW_MAX = 10
+    PA_WINDOW_COUNT_STAR = 6, PA_WINDOW_COUNT = 7, PA_WINDOW_SUM = 8, PA_WINDOW_MIN = 9, PA_WINDOW_MAX = 10,
+    /* the value functions: pa_framed_window_desc only */
+    PA_WINDOW_LAG = 11, PA_WINDOW_LEAD = 12, PA_WINDOW_FIRST_VALUE = 13, PA_WINDOW_LAST_VALUE = 14, PA_WINDOW_NTH_VALUE = 15
 } pa_window_function;
 typedef struct pa_window_function_desc {
     int32_t function;                    /* pa_window_function */
@@ -619,11 +622,12 @@ typedef struct pa_window_desc {          /* WindowOperatorFactory(sourceTypes, o
 } pa_window_desc;
 
 /* WindowOperator with frames: pa_window_desc whose functions carry a frame (FrameInfo), for the aggregate window functions count(*) /
- * count(x) / sum(x) / min(x) / max(x) next to the six ranking functions.  It builds the same operator: order, partitions, peers, the
- * output layout, the state machine, the refusal of pre-grouped / pre-sorted input and the limits of 8 partition channels and 16
- * functions are those of pa_window_desc, unchanged.  For ids 0 .. 5 the frame is range-checked and otherwise ignored, and the column is
- * bit for bit the one pa_window_create gives: a window node that mixes rank() with sum() runs in one operator and one sort.
- *   Frames: start_type must be PA_BOUND_UNBOUNDED_PRECEDING.  With i the row's place in its partition, N the partition's size and
+ * count(x) / sum(x) / min(x) / max(x) and the value functions lag / lead / first_value / last_value / nth_value next to the six ranking
+ * functions.  It builds the same operator: order, partitions, peers, the output layout, the state machine, the refusal of pre-grouped /
+ * pre-sorted input and the limits of 8 partition channels and 16 functions are those of pa_window_desc, unchanged.  For ids 0 .. 5 the
+ * frame is range-checked and otherwise ignored, and the column is bit for bit the one pa_window_create gives: a window node that mixes
+ * rank() with sum() and lag() runs in one operator and one sort.
+ *   Frames: start_type must be PA_BOUND_UNBOUNDED_PRECEDING (lag / lead: any well-formed frame, ignored).  With i the row's place in its partition, N the partition's size and
  *     [ps, pe) its peer group's places, the frame of an aggregate is the places 0 .. e:
  *       PA_FRAME_ROWS   ... PA_BOUND_CURRENT_ROW                     e = i
  *       PA_FRAME_RANGE / PA_FRAME_GROUPS ... PA_BOUND_CURRENT_ROW    e = pe - 1     (RANGE is the SQL default frame)
@@ -644,24 +648,44 @@ typedef struct pa_window_desc {          /* WindowOperatorFactory(sourceTypes, o
  *     values the first in sorted order stays.  Better: min, every type: compares < 0, for DOUBLE / REAL in Double.compare order (-0.0
  *     before +0.0, NaN largest); max over DOUBLE / REAL: value > held || isNaN(held) (NaN loses to everything, -0.0 and +0.0 tie).  A NaN
  *     result is some NaN: its payload is not part of the contract.  A BOOLEAN result is 0 or 1.
- *   At creation, before any device work, PA_ERR_INVALID_ARGUMENT first: what pa_window_desc reports; a function id outside 0 .. 10; a
+ *   Value functions (LagFunction / LeadFunction / FirstValueFunction / LastValueFunction / NthValueFunction of operator/window/), with
+ *     the arguments in argument_channels:
+ *       PA_WINDOW_LAG / LEAD                1 .. 3 channels: value, offset (optional), default (optional)
+ *       PA_WINDOW_FIRST_VALUE / LAST_VALUE  exactly 1: value
+ *       PA_WINDOW_NTH_VALUE                 exactly 2: value, offset
+ *     The value channel has any type an output channel may have, a long decimal included, except VARCHAR; the result column has its
+ *     type and holds the very bytes of the source row: -0.0, NaN payloads, BOOLEAN bytes and all 16 bytes of a long decimal pass
+ *     unchanged.  The offset channel is BIGINT or INTEGER, read at the current row; the default channel has the value channel's type
+ *     (for DECIMAL also its type parameter) and is read at the current row.
+ *     lag / lead: the frame is range-checked and otherwise ignored.  A NULL offset gives NULL; an offset < 0 makes the first
+ *     pa_op_get_output after finish fail with PA_ERR_INVALID_ARGUMENT ("Offset must be at least 0"); without an offset channel the
+ *     offset is 1.  The target place is i - offset (lag) / i + offset (lead), in 64 bits without overflow: inside [0, N) the result is
+ *     the value there, which may be NULL; else the default at the current row, which may be NULL; without a default channel NULL.
+ *     first_value / last_value / nth_value use the frame 0 .. e of the aggregates above: first_value is the value at place 0,
+ *     last_value the value at place e; nth_value: a NULL offset gives NULL, an offset < 1 fails as above with "Offset must be at
+ *     least 1", else the value at place offset - 1 when offset - 1 <= e, else NULL.  After either offset error nothing is emitted and
+ *     the operator can still be closed and destroyed.
+ *     ignore_nulls of a value function: 0 is taken, 1 (IGNORE NULLS) is well formed and PA_ERR_NOT_SUPPORTED.
+ *   At creation, before any device work, PA_ERR_INVALID_ARGUMENT first: what pa_window_desc reports; a function id outside 0 .. 15; a
  *     frame_type, start_type or end_type outside its enum; start_type PA_BOUND_UNBOUNDED_FOLLOWING; end_type
- *     PA_BOUND_UNBOUNDED_PRECEDING; a PA_BOUND_PRECEDING / PA_BOUND_FOLLOWING bound whose channel is out of range; ignore_nulls != 0; a
- *     wrong argument_count; a sum argument that is not numeric (VARCHAR, BOOLEAN, DATE).  Then PA_ERR_NOT_SUPPORTED: what pa_window_desc
- *     refuses; any other frame of an aggregate; sum over DOUBLE, REAL, DECIMAL or a long decimal; min / max over VARCHAR, a long decimal
- *     or PA_ROW; count over PA_ROW.  Value functions (lag, lead, first_value, last_value, nth_value), avg and IGNORE NULLS have no id. */
+ *     PA_BOUND_UNBOUNDED_PRECEDING; a PA_BOUND_PRECEDING / PA_BOUND_FOLLOWING bound whose channel is out of range; ignore_nulls != 0
+ *     for ids 0 .. 10, outside 0 / 1 for a value function; a wrong argument_count; a sum argument that is not numeric (VARCHAR,
+ *     BOOLEAN, DATE); an offset channel that is not BIGINT / INTEGER; a default channel whose type or DECIMAL parameter differs from
+ *     the value's.  Then PA_ERR_NOT_SUPPORTED: what pa_window_desc refuses; any other frame of an aggregate or of first_value /
+ *     last_value / nth_value; sum over DOUBLE, REAL, DECIMAL or a long decimal; min / max over VARCHAR, a long decimal or PA_ROW; count
+ *     over PA_ROW; a value function over VARCHAR or PA_ROW, or with ignore_nulls = 1.  avg has no id. */
 typedef enum pa_window_frame_type { PA_FRAME_RANGE = 0, PA_FRAME_ROWS = 1, PA_FRAME_GROUPS = 2 } pa_window_frame_type;
 typedef enum pa_window_frame_bound {
     PA_BOUND_UNBOUNDED_PRECEDING = 0, PA_BOUND_PRECEDING = 1, PA_BOUND_CURRENT_ROW = 2, PA_BOUND_FOLLOWING = 3, PA_BOUND_UNBOUNDED_FOLLOWING = 4
 } pa_window_frame_bound;
 typedef struct pa_framed_window_function_desc {
-    int32_t function;                    /* pa_window_function, 0 .. 10 */
-    int32_t argument_count;              /* ntile, count, sum, min, max: 1; else 0 */
+    int32_t function;                    /* pa_window_function, 0 .. 15 */
+    int32_t argument_count;              /* ntile, count, sum, min, max, first_value, last_value: 1; nth_value: 2; lag, lead: 1 .. 3; else 0 */
     const int32_t* argument_channels;    /* may be NULL when there are none */
     int32_t frame_type;                  /* FrameInfo.getType as a pa_window_frame_type */
     int32_t start_type, start_channel;   /* pa_window_frame_bound; channel -1 when the bound takes none */
     int32_t end_type, end_channel;
-    int32_t ignore_nulls;                /* must be 0 */
+    int32_t ignore_nulls;                /* must be 0; a value function: 0, or 1 = IGNORE NULLS (refused) */
 } pa_framed_window_function_desc;
 typedef struct pa_framed_window_desc {   /* the fields of pa_window_desc, in the same order */
     int32_t input_channel_count;

@@ -642,14 +642,15 @@ struct WindowOperatorFactory {
     }
 };
 
-// The same factory over pa_framed_window_desc: the ranking functions and count(*) / count / sum / min / max, each with its frame
-// (FrameInfo); without one, the SQL default RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
+// The same factory over pa_framed_window_desc: the ranking functions, count(*) / count / sum / min / max and lag / lead / first_value /
+// last_value / nth_value, each with its frame (FrameInfo); without one, the SQL default RANGE BETWEEN UNBOUNDED PRECEDING AND CURRENT ROW
 struct FramedWindowFunctionDefinition {
-    int32_t function = PA_WINDOW_ROW_NUMBER;   // pa_window_function, 0 .. 10
-    std::vector<int32_t> argumentChannels;     // ntile, count, sum, min, max: one channel
+    int32_t function = PA_WINDOW_ROW_NUMBER;   // pa_window_function, 0 .. 15
+    std::vector<int32_t> argumentChannels;     // ntile, count, sum, min, max, first_value, last_value: one channel; nth_value: value,
+                                               // offset; lag, lead: value, then optionally offset, then optionally default
     int32_t frameType = PA_FRAME_RANGE, startType = PA_BOUND_UNBOUNDED_PRECEDING, endType = PA_BOUND_CURRENT_ROW;
     int32_t startChannel = -1, endChannel = -1;
-    bool ignoreNulls = false;
+    bool ignoreNulls = false;                  // a value function with IGNORE NULLS: well formed, refused (PA_ERR_NOT_SUPPORTED)
 };
 struct FramedWindowOperatorFactory {
     std::vector<int32_t> sourceTypes, outputChannels;

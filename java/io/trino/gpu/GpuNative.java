@@ -96,8 +96,9 @@ final class GpuNative
     static native long createWindow(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] functions, int[] functionArguments,
             int[] partitionChannels, int[] sortChannels, int[] sortOrders, int preGroupedChannelCount, int preSortedChannelPrefix,
             int expectedPositions, int outputMem);
-    /** The same with frames: the ranking functions and count / sum / min / max (ids 6 .. 10).  frames = six ints per function:
-     *  frame type, start type, start channel, end type, end channel, ignore nulls (FrameInfo; pa_framed_window_function_desc). */
+    /** The same with frames: the ranking functions, count / sum / min / max (ids 6 .. 10) and lag / lead / first_value / last_value /
+     *  nth_value (ids 11 .. 15).  frames = six ints per function: frame type, start type, start channel, end type, end channel, ignore
+     *  nulls (FrameInfo; pa_framed_window_function_desc).  functionArguments = one channel per function or three, -1 ending a list. */
     static native long createFramedWindow(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] functions, int[] functionArguments,
             int[] frames, int[] partitionChannels, int[] sortChannels, int[] sortOrders, int preGroupedChannelCount, int preSortedChannelPrefix,
             int expectedPositions, int outputMem);

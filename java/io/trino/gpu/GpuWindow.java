@@ -22,10 +22,11 @@ import java.util.Optional;
  * RegularWindowPartition: -0.0 and +0.0 in a sort channel are peers (include/presto_amd.h).
  *
  * The overload that also takes each function's frame (the FrameInfo fields) goes through pa_framed_window_create and takes count(*) /
- * count(x) / sum(x) / min(x) / max(x) next to the ranking functions, over the frames UNBOUNDED PRECEDING .. CURRENT ROW (ROWS, RANGE,
- * GROUPS) and UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING.  It is empty for every other frame of an aggregate, for IGNORE NULLS, for sum
- * over anything but BIGINT / INTEGER, for min / max over VARCHAR, long decimals or rows, and for any other function (avg, lag, lead,
- * first_value, last_value, nth_value).
+ * count(x) / sum(x) / min(x) / max(x) and lag / lead / first_value / last_value / nth_value next to the ranking functions, over the
+ * frames UNBOUNDED PRECEDING .. CURRENT ROW (ROWS, RANGE, GROUPS) and UNBOUNDED PRECEDING .. UNBOUNDED FOLLOWING (lag and lead ignore
+ * their frame).  It is empty for every other frame of an aggregate or of first_value / last_value / nth_value, for IGNORE NULLS, for sum
+ * over anything but BIGINT / INTEGER, for min / max over VARCHAR, long decimals or rows, for a value function over VARCHAR or rows, with
+ * an offset that is not BIGINT / INTEGER or a default of another type than the value, and for any other function (avg).
  */
 public final class GpuWindow
 {
@@ -35,6 +36,8 @@ public final class GpuWindow
             PA_WINDOW_CUME_DIST = 4, PA_WINDOW_NTILE = 5;
     private static final int PA_DATE = 2, PA_DOUBLE = 3, PA_BOOLEAN = 4, PA_REAL = 7, PA_DECIMAL = 8;
     private static final int PA_WINDOW_COUNT_STAR = 6, PA_WINDOW_COUNT = 7, PA_WINDOW_SUM = 8, PA_WINDOW_MIN = 9, PA_WINDOW_MAX = 10;
+    private static final int PA_VARCHAR = 5;
+    private static final int PA_WINDOW_LAG = 11, PA_WINDOW_LEAD = 12, PA_WINDOW_FIRST_VALUE = 13, PA_WINDOW_LAST_VALUE = 14, PA_WINDOW_NTH_VALUE = 15;
     // pa_window_frame_type = WindowFrameType.ordinal(), pa_window_frame_bound = FrameBoundType.ordinal()
     private static final int PA_BOUND_UNBOUNDED_PRECEDING = 0, PA_BOUND_CURRENT_ROW = 2, PA_BOUND_UNBOUNDED_FOLLOWING = 4;
     private static final int MAX_FUNCTIONS = 16;
@@ -158,6 +161,25 @@ public final class GpuWindow
         }
     }
 
+    /** pa_window_function of a value window function by name and argument count, or -1 */
+    static int valueFunctionOf(String name, int argumentCount)
+    {
+        switch (name.toLowerCase(Locale.ENGLISH)) {
+            case "lag":
+                return argumentCount >= 1 && argumentCount <= 3 ? PA_WINDOW_LAG : -1;
+            case "lead":
+                return argumentCount >= 1 && argumentCount <= 3 ? PA_WINDOW_LEAD : -1;
+            case "first_value":
+                return argumentCount == 1 ? PA_WINDOW_FIRST_VALUE : -1;
+            case "last_value":
+                return argumentCount == 1 ? PA_WINDOW_LAST_VALUE : -1;
+            case "nth_value":
+                return argumentCount == 2 ? PA_WINDOW_NTH_VALUE : -1;
+            default:
+                return -1;
+        }
+    }
+
     /** the window node with each function's frame, whether it ignores NULLs, and its argument types (which the channels' types repeat) */
     public static Optional<OperatorFactory> window(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> outputChannels,
             List<String> functionNames, List<List<Integer>> functionArgumentChannels, List<List<Type>> functionArgumentTypes, List<Frame> frames,
@@ -181,7 +203,8 @@ public final class GpuWindow
             return Optional.empty();
         }
         int[] functions = new int[count];
-        int[] arguments = new int[count];
+        int[] arguments = new int[3 * count];   // three channels per function: value / argument, offset, default; -1 ends the list
+        java.util.Arrays.fill(arguments, -1);
         int[] frameWords = new int[6 * count];
         List<Type> output = new ArrayList<>();
         for (int channel : outputChannels) {
@@ -193,13 +216,32 @@ public final class GpuWindow
         for (int i = 0; i < count; i++) {
             List<Integer> args = functionArgumentChannels.get(i);
             Frame frame = frames.get(i);
-            if (args.size() != functionArgumentTypes.get(i).size() || args.size() > 1 || ignoreNulls.get(i)) {
+            int value = valueFunctionOf(functionNames.get(i), args.size());
+            if (args.size() != functionArgumentTypes.get(i).size() || args.size() > (value >= 0 ? 3 : 1) || ignoreNulls.get(i)) {
                 return Optional.empty();
             }
-            arguments[i] = args.isEmpty() ? -1 : args.get(0);
-            int argument = args.isEmpty() ? -1 : types[arguments[i]];
+            for (int k = 0; k < args.size(); k++) {
+                arguments[3 * i + k] = args.get(k);
+            }
+            int argument = args.isEmpty() ? -1 : types[arguments[3 * i]];
             functions[i] = functionOf(functionNames.get(i));
-            if (functions[i] >= 0) {
+            if (value >= 0) {
+                functions[i] = value;
+                boolean shift = value == PA_WINDOW_LAG || value == PA_WINDOW_LEAD;
+                boolean prefix = frame.startType == PA_BOUND_UNBOUNDED_PRECEDING
+                        && (frame.endType == PA_BOUND_CURRENT_ROW || frame.endType == PA_BOUND_UNBOUNDED_FOLLOWING);
+                if (argument == PA_VARCHAR || argument == PA_ROW || (!shift && !prefix)) {
+                    return Optional.empty();
+                }
+                if (args.size() >= 2 && types[args.get(1)] != PA_BIGINT && types[args.get(1)] != PA_INTEGER) {
+                    return Optional.empty();
+                }
+                if (args.size() == 3 && (types[args.get(2)] != argument || params[args.get(2)] != params[args.get(0)])) {
+                    return Optional.empty();
+                }
+                output.add(sourceTypes.get(args.get(0)));
+            }
+            else if (functions[i] >= 0) {
                 // a ranking function: the frame is passed on and ignored
                 if (args.size() != (functions[i] == PA_WINDOW_NTILE ? 1 : 0) || (argument >= 0 && argument != PA_BIGINT && argument != PA_INTEGER)) {
                     return Optional.empty();
@@ -236,7 +278,7 @@ public final class GpuWindow
                         break;
                 }
                 boolean minMax = functions[i] == PA_WINDOW_MIN || functions[i] == PA_WINDOW_MAX;
-                output.add(minMax ? sourceTypes.get(arguments[i]) : BigintType.BIGINT);
+                output.add(minMax ? sourceTypes.get(arguments[3 * i]) : BigintType.BIGINT);
             }
             frameWords[6 * i] = frame.type;
             frameWords[6 * i + 1] = frame.startType;

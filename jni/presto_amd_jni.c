@@ -696,8 +696,10 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createWindow(JNIEnv* env, jc
     return (jlong)(intptr_t)op;
 }
 
-/* The same with frames (pa_framed_window_desc): the ranking functions and count / sum / min / max.  frames = six ints per function:
- * frame_type, start_type, start_channel, end_type, end_channel, ignore_nulls (pa_window_frame_type / pa_window_frame_bound). */
+/* The same with frames (pa_framed_window_desc): the ranking functions, count / sum / min / max and the value functions.  frames = six
+ * ints per function: frame_type, start_type, start_channel, end_type, end_channel, ignore_nulls (pa_window_frame_type /
+ * pa_window_frame_bound).  functionArguments = one channel per function, or three (lag / lead: value, offset, default); -1 ends a
+ * function's list. */
 JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createFramedWindow(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams, jintArray outputChannels,
         jintArray functions, jintArray functionArguments, jintArray frames, jintArray partitionChannels, jintArray sortChannels, jintArray sortOrders,
         jint preGroupedChannelCount, jint preSortedChannelPrefix, jint expectedPositions, jint outputMem)
@@ -709,12 +711,13 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createFramedWindow(JNIEnv* e
     int32_t *fa = ints_of(env, functionArguments, &nfa), *fr = ints_of(env, frames, &nfr), *pc = ints_of(env, partitionChannels, &npc);
     int32_t *sc = ints_of(env, sortChannels, &nsc), *so = ints_of(env, sortOrders, &nso);
     int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
-    if (nf != nfa || nfr != 6 * nf) nf = 0;   /* (refused below: function_count 0) */
+    const jsize stride = nfa == 3 * nf ? 3 : 1;
+    if (nfa != stride * nf || nfr != 6 * nf) nf = 0;   /* (refused below: function_count 0) */
     pa_framed_window_function_desc* fs = (pa_framed_window_function_desc*)calloc((size_t)(nf > 0 ? nf : 1), sizeof *fs);
     for (i = 0; fs && fn && fa && fr && i < nf; i++) {
         fs[i].function = fn[i];
-        fs[i].argument_count = fa[i] >= 0 ? 1 : 0;
-        fs[i].argument_channels = fa + i;
+        while (fs[i].argument_count < stride && fa[stride * i + fs[i].argument_count] >= 0) fs[i].argument_count++;
+        fs[i].argument_channels = fa + stride * i;
         fs[i].frame_type = fr[6 * i]; fs[i].start_type = fr[6 * i + 1]; fs[i].start_channel = fr[6 * i + 2];
         fs[i].end_type = fr[6 * i + 3]; fs[i].end_channel = fr[6 * i + 4]; fs[i].ignore_nulls = fr[6 * i + 5];
     }

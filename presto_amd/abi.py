@@ -428,8 +428,9 @@ class pa_window_desc(C.Structure):
     ]
 
 
-# the aggregates and the frames of pa_framed_window_desc
+# the aggregates, the value functions and the frames of pa_framed_window_desc
 WINDOW_COUNT_STAR, WINDOW_COUNT, WINDOW_SUM, WINDOW_MIN, WINDOW_MAX = 6, 7, 8, 9, 10                                # pa_window_function
+WINDOW_LAG, WINDOW_LEAD, WINDOW_FIRST_VALUE, WINDOW_LAST_VALUE, WINDOW_NTH_VALUE = 11, 12, 13, 14, 15                 # pa_window_function
 FRAME_RANGE, FRAME_ROWS, FRAME_GROUPS = 0, 1, 2                                                                     # pa_window_frame_type
 BOUND_UNBOUNDED_PRECEDING, BOUND_PRECEDING, BOUND_CURRENT_ROW, BOUND_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4   # pa_window_frame_bound
 

@@ -1,14 +1,15 @@
 // op_window.cpp -- WindowOperator on device: the ranking functions row_number / rank / dense_rank / percent_rank / cume_dist / ntile and,
-// through the framed descriptor, count / sum / min / max over the frames that start at UNBOUNDED PRECEDING,
-// OVER (PARTITION BY ... ORDER BY ...).
+// through the framed descriptor, count / sum / min / max and lag / lead / first_value / last_value / nth_value over the frames that
+// start at UNBOUNDED PRECEDING, OVER (PARTITION BY ... ORDER BY ...).
 //
 // Reference path replaced:
 //   LocalExecutionPlanner.visitWindow
 //   WindowOperator (…/operator/WindowOperator.java: the sort :294, the partition ends :909-935) over RegularWindowPartition (peer
 //   groups :180-190) and RowNumberFunction / RankFunction / DenseRankFunction / PercentRankFunction / CumulativeDistributionFunction /
 //   NTileFunction of …/operator/window/, which ignore frames; AggregateWindowFunction over CountAggregation / CountColumn /
-//   LongSumAggregation / the min and max of AbstractMinMaxAggregationFunction.  A window node with any other function or frame stays
-//   with the reference.
+//   LongSumAggregation / the min and max of AbstractMinMaxAggregationFunction; LagFunction / LeadFunction / FirstValueFunction /
+//   LastValueFunction / NthValueFunction.  A window node with any other function or frame, IGNORE NULLS or a VARCHAR value stays with
+//   the reference.
 //
 // Contract (include/presto_amd.h).  Output only after finish: every input row, sorted by [partition channels ASC_NULLS_LAST] + [sort
 // channels], rows that compare equal in arrival order; the output channels, then one column per function.
@@ -19,8 +20,9 @@
 //   flags      one launch per channel: IS DISTINCT FROM the sorted row before (window_kernels.hpp) -> partition and peer flags;
 //   runs       two exclusive scans number the partitions and the peer groups, one pass stores where each starts;
 //   aggregates per distinct argument channel one gather into sorted order; per distinct (kind, channel) one segmented scan;
-//   functions  one pass writes every requested column by sorted index; a bad ntile bucket count and a sum outside int64 set bits of an
-//              error word, read back with the scan totals;
+//   functions  one pass writes every requested column by sorted index: a value column copies its value channel's bytes from the held
+//              row at perm[target]; a bad ntile bucket count, a sum outside int64 and a bad lag / lead / nth_value offset set bits of
+//              an error word, read back with the scan totals;
 //   output     the output channels gathered through the permutation, as OrderBy gathers them.
 #include <algorithm>
 #include <cstring>
@@ -35,18 +37,27 @@ namespace pa {
 namespace {
 
 bool is_aggregate(int32_t function) { return function >= PA_WINDOW_COUNT_STAR && function <= PA_WINDOW_MAX; }
-int32_t arguments_of(int32_t function) { return function == PA_WINDOW_NTILE || (is_aggregate(function) && function != PA_WINDOW_COUNT_STAR) ? 1 : 0; }
+bool is_value(int32_t function) { return function >= PA_WINDOW_LAG && function <= PA_WINDOW_NTH_VALUE; }
+bool is_shift(int32_t function) { return function == PA_WINDOW_LAG || function == PA_WINDOW_LEAD; }
+int32_t min_arguments_of(int32_t function)
+{
+    if (function == PA_WINDOW_NTH_VALUE) return 2;
+    return function == PA_WINDOW_NTILE || is_value(function) || (is_aggregate(function) && function != PA_WINDOW_COUNT_STAR) ? 1 : 0;
+}
+int32_t max_arguments_of(int32_t function) { return is_shift(function) ? 3 : min_arguments_of(function); }
 
 // One window function as the operator runs it, whichever descriptor it came from.
 struct FunctionSpec {
     int32_t function;
-    int32_t argument_channel;   // -1: none
-    int32_t frame_end;          // aggregates: WindowFrameEnd
+    int32_t argument_channel;   // -1: none; a value function: the value channel
+    int32_t offset_channel;     // lag / lead / nth_value; -1: none
+    int32_t default_channel;    // lag / lead; -1: none
+    int32_t frame_end;          // aggregates, first_value / last_value / nth_value: WindowFrameEnd
 };
 
 // ---- the two function descriptors: what is an invalid argument, what is refused, what the operator keeps ------------------------------
 int32_t last_function(const pa_window_function_desc&) { return PA_WINDOW_NTILE; }
-int32_t last_function(const pa_framed_window_function_desc&) { return PA_WINDOW_MAX; }
+int32_t last_function(const pa_framed_window_function_desc&) { return PA_WINDOW_NTH_VALUE; }
 
 void check_frame_arguments(const pa_window_function_desc&, int32_t) {}
 void check_frame_arguments(const pa_framed_window_function_desc& f, int32_t channels)
@@ -58,8 +69,11 @@ void check_frame_arguments(const pa_framed_window_function_desc& f, int32_t chan
     PA_REQUIRE(f.end_type != PA_BOUND_UNBOUNDED_PRECEDING, PA_ERR_INVALID_ARGUMENT, "a frame cannot end at UNBOUNDED PRECEDING");
     if (f.start_type == PA_BOUND_PRECEDING || f.start_type == PA_BOUND_FOLLOWING) check_channels(&f.start_channel, 1, channels, "frame start");
     if (f.end_type == PA_BOUND_PRECEDING || f.end_type == PA_BOUND_FOLLOWING) check_channels(&f.end_channel, 1, channels, "frame end");
-    PA_REQUIRE(f.ignore_nulls == 0, PA_ERR_INVALID_ARGUMENT, "IGNORE NULLS is not taken");
+    if (is_value(f.function)) PA_REQUIRE(f.ignore_nulls == 0 || f.ignore_nulls == 1, PA_ERR_INVALID_ARGUMENT, "ignore_nulls is 0 or 1");
+    else PA_REQUIRE(f.ignore_nulls == 0, PA_ERR_INVALID_ARGUMENT, "IGNORE NULLS is not taken");
 }
+bool ignore_nulls_of(const pa_window_function_desc&) { return false; }
+bool ignore_nulls_of(const pa_framed_window_function_desc& f) { return f.ignore_nulls != 0; }
 
 // (the frames the device path takes are a prefix of the partition; -1: another frame)
 int32_t frame_end_of(const pa_window_function_desc&) { return kWindowFramePartition; }
@@ -71,26 +85,47 @@ int32_t frame_end_of(const pa_framed_window_function_desc& f)
     return f.frame_type == PA_FRAME_ROWS ? kWindowFrameRow : kWindowFramePeers;
 }
 
+// (params: the channels' type parameters, or null = all 0)
 template <class F>
-void check_function_arguments(const F& f, int32_t channels, const int32_t* types)
+void check_function_arguments(const F& f, int32_t channels, const int32_t* types, const int32_t* params)
 {
     PA_REQUIRE(f.function >= PA_WINDOW_ROW_NUMBER && f.function <= last_function(f), PA_ERR_INVALID_ARGUMENT, "unknown window function");
     check_frame_arguments(f, channels);
-    PA_REQUIRE(f.argument_count == arguments_of(f.function), PA_ERR_INVALID_ARGUMENT, "wrong number of window function arguments");
+    PA_REQUIRE(f.argument_count >= min_arguments_of(f.function) && f.argument_count <= max_arguments_of(f.function), PA_ERR_INVALID_ARGUMENT,
+               "wrong number of window function arguments");
     if (f.argument_count == 0) return;
     PA_REQUIRE(f.argument_channels != nullptr, PA_ERR_INVALID_ARGUMENT, "argument channels are null");
-    check_channels(f.argument_channels, 1, channels, "argument");
+    check_channels(f.argument_channels, f.argument_count, channels, "argument");
     const int32_t t = types[f.argument_channels[0]];
     if (f.function == PA_WINDOW_NTILE) PA_REQUIRE(t == PA_BIGINT || t == PA_INTEGER, PA_ERR_INVALID_ARGUMENT, "ntile takes a BIGINT or INTEGER argument");
     if (f.function == PA_WINDOW_SUM) PA_REQUIRE(t != PA_VARCHAR && t != PA_BOOLEAN && t != PA_DATE, PA_ERR_INVALID_ARGUMENT, "sum takes a numeric argument");
+    if (!is_value(f.function)) return;
+    if (f.argument_count >= 2) {
+        const int32_t o = types[f.argument_channels[1]];
+        PA_REQUIRE(o == PA_BIGINT || o == PA_INTEGER, PA_ERR_INVALID_ARGUMENT, "a window function offset is BIGINT or INTEGER");
+    }
+    if (f.argument_count >= 3) {
+        const int32_t v = f.argument_channels[0], d = f.argument_channels[2];
+        const bool parametrised = t == PA_DECIMAL || t == PA_LONG_DECIMAL;
+        PA_REQUIRE(types[d] == t && (!parametrised || params == nullptr || params[d] == params[v]), PA_ERR_INVALID_ARGUMENT,
+                   "the default of lag / lead has the value's type");
+    }
 }
 
 // what the device path does not take of a function that is well formed
 template <class F>
 void check_function_supported(const F& f, const int32_t* types)
 {
-    if (!is_aggregate(f.function)) return;
+    if (is_value(f.function)) {
+        const int32_t t = types[f.argument_channels[0]];
+        PA_REQUIRE(!ignore_nulls_of(f), PA_ERR_NOT_SUPPORTED, "IGNORE NULLS");
+        PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "a value window function over a VARCHAR argument");
+        check_carried_type(t, "value function argument");
+        if (is_shift(f.function)) return;   // (the frame is not read)
+    }
+    else if (!is_aggregate(f.function)) return;
     PA_REQUIRE(frame_end_of(f) >= 0, PA_ERR_NOT_SUPPORTED, "window frame outside UNBOUNDED PRECEDING .. CURRENT ROW / UNBOUNDED FOLLOWING");
+    if (is_value(f.function)) return;
     if (f.function == PA_WINDOW_COUNT_STAR) return;
     const int32_t t = types[f.argument_channels[0]];
     if (f.function == PA_WINDOW_COUNT) check_carried_type(t, "count argument");
@@ -107,7 +142,8 @@ void check_function_supported(const F& f, const int32_t* types)
 template <class F>
 FunctionSpec spec_of(const F& f)
 {
-    return FunctionSpec{f.function, f.argument_count > 0 ? f.argument_channels[0] : -1, frame_end_of(f)};
+    auto channel = [&f](int32_t k) { return f.argument_count > k ? f.argument_channels[k] : -1; };
+    return FunctionSpec{f.function, channel(0), channel(1), channel(2), frame_end_of(f)};
 }
 
 // checked before the device is asked for: a shape the device path does not take is reported as such with or without a GPU
@@ -132,7 +168,7 @@ void* checked_stream(const Desc* d)
         check_channels(d->sort_channels + i, 1, channels, "sort");
         PA_REQUIRE(d->sort_orders[i] >= 0 && d->sort_orders[i] <= 3, PA_ERR_INVALID_ARGUMENT, "unknown sort order");
     }
-    for (int32_t i = 0; i < d->function_count; i++) check_function_arguments(d->functions[i], channels, types);
+    for (int32_t i = 0; i < d->function_count; i++) check_function_arguments(d->functions[i], channels, types, d->input_type_params);
     PA_REQUIRE(d->expected_positions >= 0, PA_ERR_INVALID_ARGUMENT, "expected_positions is negative");
     check_output_mem(d->output_mem);
     // what the device path does not take
@@ -170,7 +206,8 @@ public:
         for (int32_t c : order_channels_) needed_[c] = true;
         for (int32_t c : output_channels_) needed_[c] = true;
         for (const FunctionSpec& f : functions_)
-            if (f.argument_channel >= 0) needed_[f.argument_channel] = true;
+            for (int32_t c : {f.argument_channel, f.offset_channel, f.default_channel})
+                if (c >= 0) needed_[c] = true;
         held_.init(types_, needed_);
         timer.set_name("k_window_functions");
     }
@@ -251,13 +288,33 @@ public:
             f.function = spec.function;
             f.frame_end = spec.frame_end;
             const bool min_max = spec.function == PA_WINDOW_MIN || spec.function == PA_WINDOW_MAX;
-            oc.type = min_max ? types_[spec.argument_channel]
+            const bool value = is_value(spec.function);
+            oc.type = min_max || value ? types_[spec.argument_channel]
                               : spec.function == PA_WINDOW_PERCENT_RANK || spec.function == PA_WINDOW_CUME_DIST ? PA_DOUBLE : PA_BIGINT;
             f.out = oc.values.ensure((size_t)n * (size_t)type_width(oc.type));
             if (spec.argument_channel < 0) continue;
             const OutColumn& arg = held_.cols[spec.argument_channel];
             f.arg_type = arg.type;
-            if (is_aggregate(spec.function)) {
+            if (value) {
+                // the value channel by held row at its own width; offset and default at the current row
+                f.width = type_width(oc.type);
+                f.arg_values = arg.values.ptr();
+                if (arg.has_nulls) f.arg_nulls = arg.nulls.as<uint8_t>();
+                if (spec.offset_channel >= 0) {
+                    const OutColumn& offset = held_.cols[spec.offset_channel];
+                    f.offset_type = offset.type;
+                    f.offset_values = offset.values.ptr();
+                    if (offset.has_nulls) f.offset_nulls = offset.nulls.as<uint8_t>();
+                }
+                if (spec.default_channel >= 0) {
+                    const OutColumn& fallback = held_.cols[spec.default_channel];
+                    f.default_values = fallback.values.ptr();
+                    if (fallback.has_nulls) f.default_nulls = fallback.nulls.as<uint8_t>();
+                }
+                // first_value / last_value over a channel without NULLs never give NULL
+                if (!arg.has_nulls && (spec.function == PA_WINDOW_FIRST_VALUE || spec.function == PA_WINDOW_LAST_VALUE)) continue;
+            }
+            else if (is_aggregate(spec.function)) {
                 // (count over a channel without NULLs needs no scan: it is the frame's size)
                 f.count = static_cast<const int32_t*>(scan_of(scans, kWindowScanCount, spec.argument_channel));
                 if (spec.function == PA_WINDOW_COUNT) continue;
@@ -279,6 +336,8 @@ public:
         PA_REQUIRE(h_words[0] >= 0 && h_words[0] <= h_words[1] && h_words[1] < n, PA_ERR_DEVICE, "window: run counts out of range");
         PA_REQUIRE((h_words[2] & kWindowErrorBuckets) == 0, PA_ERR_INVALID_ARGUMENT, "Buckets must be greater than 0");
         PA_REQUIRE((h_words[2] & kWindowErrorSum) == 0, PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "bigint addition overflow in a window sum");
+        PA_REQUIRE((h_words[2] & kWindowErrorLagOffset) == 0, PA_ERR_INVALID_ARGUMENT, "Offset must be at least 0");
+        PA_REQUIRE((h_words[2] & kWindowErrorNthOffset) == 0, PA_ERR_INVALID_ARGUMENT, "Offset must be at least 1");
         // the output channels in sorted order (PagesIndex.appendTo)
         held_.gather_sorted(perm, n, output_channels_, nullptr, out_cols_, scan_temp_, words + 4, s);
         publish_output(out_cols_, n, output_mem_, s, out, storage_);

@@ -299,6 +299,75 @@ __global__ __launch_bounds__(256) void k_window_functions(WindowFunctionArgs a)
                     }
                     break;
                 }
+                case PA_WINDOW_LAG:
+                case PA_WINDOW_LEAD:
+                case PA_WINDOW_FIRST_VALUE:
+                case PA_WINDOW_LAST_VALUE:
+                case PA_WINDOW_NTH_VALUE: {
+                    // the place the value is copied from, inside [0, N); lag / lead outside it: the default at the current row
+                    const bool shifted = f.function == PA_WINDOW_LAG || f.function == PA_WINDOW_LEAD;
+                    const i64 e = f.frame_end == kWindowFrameRow ? place : f.frame_end == kWindowFramePeers ? pe - 1 : N - 1;
+                    i64 row = 0;   // the current row as held: where the offset and the default are read
+                    if (f.offset_values || f.default_values) {
+                        row = a.perm[i];
+                        row = row < 0 ? 0 : row > (i64)n - 1 ? (i64)n - 1 : row;
+                    }
+                    i64 offset = 1;
+                    bool is_null = false, use_default = false;
+                    if (f.offset_values) {
+                        is_null = f.offset_nulls && f.offset_nulls[row];
+                        offset = f.offset_type == PA_BIGINT ? ((const i64*)f.offset_values)[row] : (i64)((const i32*)f.offset_values)[row];
+                    }
+                    i64 target = 0;
+                    if (f.function == PA_WINDOW_LAST_VALUE) target = e;
+                    else if (shifted && !is_null) {
+                        // (offset against the rows in front of / behind the place: place - offset, place + offset could leave int64)
+                        const i64 room = f.function == PA_WINDOW_LAG ? place : N - 1 - place;
+                        if (offset < 0) {
+                            atomicOr(a.error, kWindowErrorLagOffset);
+                            is_null = true;
+                        }
+                        else if (offset > room) use_default = true;
+                        else target = f.function == PA_WINDOW_LAG ? place - offset : place + offset;
+                    }
+                    else if (f.function == PA_WINDOW_NTH_VALUE && !is_null) {
+                        if (offset < 1) {
+                            atomicOr(a.error, kWindowErrorNthOffset);
+                            is_null = true;
+                        }
+                        else if (offset - 1 > e) is_null = true;
+                        else target = offset - 1;
+                    }
+                    const void* values = f.arg_values;
+                    const u8* nulls = f.arg_nulls;
+                    i64 src = row;
+                    if (use_default) {
+                        values = f.default_values;
+                        nulls = f.default_nulls;
+                        if (!values) is_null = true;
+                    }
+                    else if (!is_null) {
+                        i64 at = first + target;
+                        at = at < 0 ? 0 : at > (i64)n - 1 ? (i64)n - 1 : at;
+                        src = a.perm[at];
+                        src = src < 0 ? 0 : src > (i64)n - 1 ? (i64)n - 1 : src;
+                    }
+                    if (!is_null && nulls && nulls[src]) is_null = true;
+                    // the very bytes of the source row at the type's width; a NULL result holds zeros
+                    switch (f.width) {
+                        case 1: ((u8*)f.out)[i] = is_null ? (u8)0 : ((const u8*)values)[src]; break;
+                        case 4: ((u32*)f.out)[i] = is_null ? 0u : ((const u32*)values)[src]; break;
+                        case 8: ((u64*)f.out)[i] = is_null ? 0ULL : ((const u64*)values)[src]; break;
+                        default: {
+                            const u64 lo = is_null ? 0ULL : ((const u64*)values)[2 * src], hi = is_null ? 0ULL : ((const u64*)values)[2 * src + 1];
+                            ((u64*)f.out)[2 * i] = lo;
+                            ((u64*)f.out)[2 * i + 1] = hi;
+                            break;
+                        }
+                    }
+                    if (f.out_nulls) f.out_nulls[i] = is_null ? (u8)1 : (u8)0;
+                    break;
+                }
                 default: break;
             }
         }

@@ -12,13 +12,18 @@
 //             set -- tile aggregates, the scan of the tile aggregates, apply: three launches, as scan_kernels.hip scans.
 //   functions per row: its partition p and peer group q, part_start[p], part_start[p + 1], peer_start[q], peer_start[q + 1] and the
 //             peer group of part_start[p]; every requested column written by sorted index.  An aggregate column reads the scanned state
-//             at the last row of its frame: part_start[p] + e, an index that never decreases with i.
+//             at the last row of its frame: part_start[p] + e, an index that never decreases with i.  A value column (lag, lead,
+//             first_value, last_value, nth_value) copies the value channel's bytes, at the type's own width, from the held row
+//             perm[part_start[p] + target]: not through the aggregates' gather, which holds 8 bytes and widens REAL.
 // Every array element has one writer per launch and no pass reads what the same launch writes: nothing is carried between workgroups
 // and nothing depends on the order in which waves run.  Algorithmic bytes per row: flags 4 (perm) + two random rows per channel,
 // scans 2 x (4 + 4), starts 16, functions 16 + 8 per column (+ 4 + the argument through perm for ntile); the start arrays are read at
 // indices that never decrease with i.  Aggregates: gather 4 (perm) + a random value (and NULL byte) + 8 (+ 1) written; a scan reads its
 // input and part_flag twice (8 + 4 (+ 1) each time) and writes 8 (sum, min, max) or 4 (the non-null count); the function pass reads
-// 8 (+ 4 with NULLs) more per aggregate column.
+// 8 (+ 4 with NULLs) more per aggregate column.  Value functions, per column: 4 (perm at the target: one entry per partition for
+// first_value, a shifted run for lag / lead with a constant offset) + one random value of the type's width (+ its NULL byte) read, the
+// width (+ 1) written; with an offset or default channel 4 more (perm at the row itself) + the random offset (4 / 8 (+ 1)) and, where
+// the target leaves the partition, the random default.
 #pragma once
 
 #include "common.hpp"
@@ -54,7 +59,7 @@ enum WindowScanKind {
     kWindowScanMin = 2,     // out: 8 bytes per row, the first best of those rows' values (unspecified while there is none)
     kWindowScanMax = 3
 };
-constexpr int32_t kWindowErrorBuckets = 1, kWindowErrorSum = 2;   // bits of the error word
+constexpr int32_t kWindowErrorBuckets = 1, kWindowErrorSum = 2, kWindowErrorLagOffset = 4, kWindowErrorNthOffset = 8;   // bits of the error word
 // bytes of `temp` for n rows: the tile aggregates and their exclusive scan
 size_t window_scan_temp_bytes(int32_t n);
 // floating: the values are doubles' bits (min in Double.compare order; max: NaN loses to everything, the zeros tie), else int64
@@ -66,27 +71,37 @@ enum WindowFrameEnd { kWindowFrameRow = 0, kWindowFramePeers = 1, kWindowFramePa
 struct WindowFunction {
     int32_t function;          // pa_window_function
     int32_t arg_type;          // ntile: PA_BIGINT / PA_INTEGER; min / max: the argument's type = the output's
-    const void* arg_values;    // ntile: the argument channel by held row
+    int32_t frame_end;         // aggregates, first_value / last_value / nth_value: WindowFrameEnd
+    int32_t offset_type;       // PA_BIGINT / PA_INTEGER
+    int32_t width;             // value functions: bytes of one value, 1 / 4 / 8 / 16
+    const void* arg_values;    // ntile: the argument channel by held row; value functions: the value channel by held row
     const uint8_t* arg_nulls;  // may be null
-    void* out;                 // by sorted index, n x 8 bytes: BIGINT, or DOUBLE for percent_rank / cume_dist; min / max: n x the type's width
-    uint8_t* out_nulls;        // ntile with arg_nulls, sum / min / max with `count`: n bytes; else null
-    int32_t frame_end;         // aggregates: WindowFrameEnd
+    void* out;                 // by sorted index, n x 8 bytes: BIGINT, or DOUBLE for percent_rank / cume_dist; min / max, value functions: n x the type's width
+    uint8_t* out_nulls;        // ntile with arg_nulls, sum / min / max with `count`, every lag / lead / nth_value, first_value / last_value with arg_nulls:
+                               // n bytes; else null
     const void* scan;          // sum / min / max: the scanned state by sorted index
     const int32_t* count;      // count / sum / min / max: the scanned non-null count; null when the argument has no NULLs
+    const void* offset_values;     // lag / lead (null: the offset is 1), nth_value: the offset channel by held row
+    const uint8_t* offset_nulls;   // may be null
+    const void* default_values;    // lag / lead: the default channel by held row, of the value's type; null: NULL
+    const uint8_t* default_nulls;  // may be null
 };
+// (passed by value as the kernel's argument: 72 + 16 x 104 = 1736 bytes, under the 4 KB a launch takes)
 struct WindowFunctionArgs {
-    const int32_t* perm;       // sorted index -> held row (read for ntile only)
+    const int32_t* perm;       // sorted index -> held row (read for ntile and the value functions)
     const int32_t* part_flag;
     const int32_t* part_index;
     const int32_t* peer_flag;
     const int32_t* peer_index;
     const int32_t* part_start;
     const int32_t* peer_start;
-    int32_t* error;            // a row whose ntile bucket count is <= 0 ORs kWindowErrorBuckets into it
+    int32_t* error;            // a row whose ntile bucket count is <= 0 ORs kWindowErrorBuckets into it; a lag / lead offset < 0
+                               // kWindowErrorLagOffset, an nth_value offset < 1 kWindowErrorNthOffset
     int32_t n;
     int32_t count;
     WindowFunction f[kWindowMaxFunctions];
 };
+static_assert(sizeof(WindowFunction) == 104 && sizeof(WindowFunctionArgs) == 1736, "WindowFunctionArgs: the size the comment states");
 void launch_window_functions(const WindowFunctionArgs& a, hipStream_t s);
 
 }  // namespace pa

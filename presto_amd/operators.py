@@ -998,9 +998,11 @@ DEFAULT_FRAME = (abi.FRAME_RANGE, abi.BOUND_UNBOUNDED_PRECEDING, abi.BOUND_CURRE
 
 def FramedWindowOperatorFactory(input_types, output_channels, functions, partition_channels, sort_channels, sort_orders, pre_grouped_channel_count=0,
                                 pre_sorted_channel_prefix=0, expected_positions=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
-    """WindowOperatorFactory over pa_framed_window_desc: the ranking functions and count(*) / count / sum / min / max, each with its frame.
+    """WindowOperatorFactory over pa_framed_window_desc: the ranking functions, count(*) / count / sum / min / max and lag / lead /
+    first_value / last_value / nth_value, each with its frame.
     functions: an abi.WINDOW_* id, (id, [argument channels]) or (id, [argument channels], (frame_type, start_type, end_type)); a frame
-    may also be (frame_type, start_type, end_type, start_channel, end_channel, ignore_nulls).  No frame: DEFAULT_FRAME."""
+    may also be (frame_type, start_type, end_type, start_channel, end_channel, ignore_nulls).  No frame: DEFAULT_FRAME.  Argument
+    channels: lag / lead [value, offset (optional), default (optional)], first_value / last_value [value], nth_value [value, offset]."""
     d = abi.pa_framed_window_desc()
     types = abi.int32_array(input_types)
     oc = abi.int32_array(output_channels)
