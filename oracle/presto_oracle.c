@@ -520,8 +520,14 @@ static orc_val eval_arith(eval_ctx* cx, int32_t op, int32_t type, const orc_val*
             ovf = __builtin_sub_overflow((int64_t)0, x, &z);
             break;
     }
-    if (!ovf && type != PA_BIGINT && (z > INT32_MAX || z < INT32_MIN)) {
-        ovf = 1; /* IntegerOperators: Math.addExact(int,int) */
+    if (type != PA_BIGINT && (op == PA_OP_DIVIDE || op == PA_OP_MODULUS)) {
+        /* IntegerOperators.java:81-101: divide / modulus are plain long operations without a range check; MIN / -1 = 2147483648 is
+         * no error, and IntegerType narrows it to MIN when it is written to a block.  Narrowed here, at the division, as the device
+         * does (an enclosing expression sees MIN). */
+        z = (int64_t)(int32_t)z;
+    }
+    else if (!ovf && type != PA_BIGINT && (z > INT32_MAX || z < INT32_MIN)) {
+        ovf = 1; /* IntegerOperators.java:43-77, :103-113: Math.addExact / subtractExact / multiplyExact / negateExact on ints */
     }
     if (ovf) {
         cx->error = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
@@ -677,6 +683,12 @@ static orc_val eval_node(eval_ctx* cx, int32_t id)
                 else if (n->type == PA_BIGINT && type_is_int(a.type)) {
                     r.i = a.i;
                 }
+                else if (n->type == PA_INTEGER && a.type == PA_BIGINT) { /* BigintOperators.castToInteger (:129-137): toIntExact */
+                    if (a.i > INT32_MAX || a.i < INT32_MIN) {
+                        cx->error = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
+                    }
+                    r.i = a.i;
+                }
                 else if (n->type == a.type) {
                     r = a;
                 }
@@ -717,6 +729,9 @@ static orc_val eval_node(eval_ctx* cx, int32_t id)
                 }
                 case PA_FORM_BETWEEN: { /* BetweenCodeGenerator.java:64-68: value >= min AND value <= max */
                     orc_val v = eval_node(cx, args[0]);
+                    if (v.is_null) { /* :72-77: a NULL value is the result; neither bound is evaluated */
+                        return null_of(PA_BOOLEAN);
+                    }
                     orc_val lo = eval_node(cx, args[1]);
                     orc_val c1 = eval_compare(cx, PA_OP_GREATER_THAN_OR_EQUAL, &v, &lo);
                     if (!c1.is_null && !c1.i) {
@@ -2638,8 +2653,9 @@ static inline int topn_cmp(const topn_ctx* c, int32_t i, int32_t j)   /* < 0: ro
     if (d != 0) return -d;
     return c->k[i] < c->k[j] ? -1 : (c->k[i] > c->k[j] ? 1 : 0);
 }
-static int topn_qsort_cmp_ctx_set;
-static const topn_ctx* topn_qsort_ctx;
+/* qsort takes no context argument: the comparator finds it here.  Per thread -- callers sort side by side (bench.py runs one Q3 per
+ * core), and a pointer shared between them would let one thread's comparator read another call's arrays after that call returned */
+static __thread const topn_ctx* topn_qsort_ctx;
 static int topn_qsort_cmp(const void* a, const void* b)
 {
     const int c = topn_cmp(topn_qsort_ctx, *(const int32_t*)a, *(const int32_t*)b);
@@ -2676,7 +2692,6 @@ int32_t orc_topn_double_desc_bigint_asc(const double* values, const int64_t* key
             }
         }
     }
-    (void)topn_qsort_cmp_ctx_set;
     topn_qsort_ctx = &c;
     qsort(heap, (size_t)size, sizeof(int32_t), topn_qsort_cmp);
     memcpy(out_positions, heap, sizeof(int32_t) * (size_t)size);

@@ -393,7 +393,14 @@ GenValue RowCodegen::emit_node(const OwnedExpr& e, int32_t id, std::ostringstrea
                 case PA_OP_MODULUS: call = "pa_mod_exact(" + x.v + ", " + y.v + ", " + err_ + ")"; break;
                 default: call = "pa_sub_exact(0LL, " + x.v + ", " + err_ + ")"; break;
             }
-            if (n.type != PA_BIGINT) call = "pa_int_range(" + call + ", " + err_ + ")";
+            // IntegerOperators.java:43-113: add / subtract / multiply / negate are Math.*Exact on ints; divide and modulus are plain long
+            // operations with no range check (:81-101).  MIN / -1 is 2147483648 and no error there, and IntegerType narrows it to MIN
+            // when it is written to a block: narrowed here, at the division (an enclosing expression sees MIN).
+            // The long division's own MIN64 / -1 check never fires on 32-bit operands; a remainder is always in range.
+            if (n.type != PA_BIGINT) {
+                if (n.op == PA_OP_DIVIDE) call = "(i64)(i32)" + call;
+                else if (n.op != PA_OP_MODULUS) call = "pa_int_range(" + call + ", " + err_ + ")";
+            }
             out << "i64 " << r.v << " = " << (r.nullable() ? "(" + r.n + ") ? 0LL : " : "") << call << ";\n";
             return r;
         }

@@ -411,6 +411,14 @@ public:
     FilterProjectOperator(const pa_filter_project_desc* d, FpSpec spec) : spec_(std::move(spec)), stream_(d->stream)
     {
         require_device();
+        // an expression the generator does not take (mixed operand types, a CAST or a DECIMAL operator that is not on the device path)
+        // is refused here, when the operator is created, not at its first page: kernels are generated per column-layout signature,
+        // and no refusal depends on the signature
+        if (!spec_.join) {
+            std::vector<ChannelLayout> dry(spec_.n_in);
+            for (int c = 0; c < spec_.n_in; c++) dry[c].type = spec_.in_types[c];
+            (void)generate_fp(spec_, dry);
+        }
         ctl_ = static_cast<int32_t*>(ctl_buf_.ensure(64));  // [0] err [1] selected count
         PA_HIP(hipMemsetAsync(ctl_, 0, 64, stream_.get()));
         h_ctl_ = static_cast<int32_t*>(h_ctl_buf_.ensure(64));
