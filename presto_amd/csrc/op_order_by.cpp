@@ -2,25 +2,20 @@
 // input page (PagesIndex.addPage), sort by (sortChannels, sortOrders) when the input ends (PagesIndex.sort ->
 // PagesIndexOrdering with SimplePagesIndexComparator), emit the output channels in order.
 //
-// The reference quick-sorts row addresses with a multi-channel comparator.  Here: a stable least-significant-digit radix
-// sort of a row permutation on device.  Every sort channel is turned into order-preserving 64-bit images
-// (topn_kernels.hip: integers, DATE, BOOLEAN, DOUBLE in Double.compare order; a VARCHAR as its 8-byte chunks, zero padded,
-// with the length as the least significant key -- Slice.compareTo: unsigned bytes, a proper prefix sorts first) plus a
-// one-bit NULL digit above them (SortOrder: NULLS FIRST / LAST, independent of ASC / DESC); channels are processed from the
-// last sort channel to the first, each image by one stable sort of (image, row id) pairs over the bits in which the images
-// differ (sort_kernels.hip), the NULL digit by the stable partition the exchange already uses.  Fully tied rows keep arrival
-// order.  A first sort channel of integers without NULL rows that is also an output channel is written from the sorted images.
-// The rows are collected in, and the output channels gathered out of, a HeldRows (held_rows.hpp).
+// The reference quick-sorts row addresses with a multi-channel comparator.  Here the rows are collected in a HeldRows
+// (held_rows.hpp), a RowSorter (row_sort.hpp) sorts a row permutation over its columns -- stable, so fully tied rows keep
+// arrival order -- and the output channels are gathered out of the HeldRows through the permutation.  What this file adds to
+// the sort: pages that stay where they are are listed instead of copied (one alone is sorted in place); flat 4- / 8-byte
+// output channels without NULL rows are offered to the sorter as riding payload (SortCarry) and taken from it when they rode;
+// a first sort channel of integers without NULL rows that is also an output channel is written from the sorted images.
 #include <algorithm>
 #include <cstring>
 
 #include "held_rows.hpp"
 #include "keyed_operator.hpp"
 #include "operator.hpp"
-#include "scan_kernels.hpp"
-#include "sort_kernels.hpp"
+#include "row_sort.hpp"
 #include "static_kernels.hpp"
-#include "topn_kernels.hpp"
 
 namespace pa {
 
@@ -181,146 +176,55 @@ public:
         }
         else flush_held();
         const int64_t n = store_.rows;
-        int32_t* perm = static_cast<int32_t*>(perm_[0].ensure((size_t)n * 4));
-        int32_t* next = static_cast<int32_t*>(perm_[1].ensure((size_t)n * 4));
-        int32_t* digits = static_cast<int32_t*>(digits_.ensure((size_t)n * 4));
-        int32_t* pos = static_cast<int32_t*>(pos_.ensure((size_t)n * 4));
-        int64_t* counts = static_cast<int64_t*>(counts_.ensure(256 * 8));
-        uint64_t* keys = static_cast<uint64_t*>(keys_.ensure((size_t)n * 8));
-        void* temp = part_temp_.ensure(partition_temp_bytes(n, 256));
-        timer.begin(s);
-        bool identity = true;  // the permutation is still 0, 1, 2, ...: the images are in the current order as they are, and perm is not
-                               // written yet (the first sort takes the row ids as implied; whoever else needs them writes them first)
-        bool written = false;
-        auto materialize = [&] {
-            if (identity && !written) launch_iota_i32(perm, n, s);
-            written = true;
-        };
-        auto pass = [&](int partitions) {
-            // one stable radix pass: rows grouped by digit, arrival order kept inside a digit; perm' = perm o pos
-            launch_partition_positions(digits, n, partitions, pos, counts, temp, s);
-            materialize();
-            launch_gather_flat(perm, 4, pos, n, next, s);
-            std::swap(perm, next);
-            identity = false;
-        };
-        // Stable sort of (image, row id) PAIRS: the images are brought into the current order once (one gather), then the pairs are sorted
-        // by the bits in which the images differ at all (OR / AND of the images: keys below 2^40 are sorted by 40 bits, not 64) --
-        // launch_sort_pairs, sort_kernels.hip.  The first version sorted the permutation alone and fetched every pass's digits through
-        // it (a random 8-byte read per row and pass: 2^24 rows by a BIGINT key 6.5 ms), the second regrouped the pairs in eight LDS-staged
-        // 8-bit passes of its own (count, scan, scatter: 2.3 ms).
-        uint64_t* kp[2] = {static_cast<uint64_t*>(pair_keys_[0].ensure((size_t)n * 8)), static_cast<uint64_t*>(pair_keys_[1].ensure((size_t)n * 8))};
         // Output channels that can ride along with the pairs of the LAST sort (the first sort channel's) instead of being gathered by the
-        // sorted row ids afterwards: flat 4- / 8-byte channels without NULL rows, when that sort starts from the identity permutation (one
-        // sort channel, or the channels behind it all constant) and no NULL digit follows it.  payload_of[j] = its slot, or -1.
+        // sorted row ids afterwards: flat 4- / 8-byte channels without NULL rows.  Whether they do is the sorter's to say (carry.moved: that
+        // sort started from the identity permutation -- one sort channel, or the channels behind it all constant -- and the hand-written
+        // sort took it).  payload_of[j] = its slot, or -1.
         const std::vector<int>& outs = output_channels_;
         std::vector<int> payload_of(outs.size(), -1);
-        SortPayload payload;
-        memset(&payload, 0, sizeof payload);
-        {
-            const OutColumn& f = store_.cols[(size_t)sort_channels_[0]];
-            const bool images_serve = !f.varwidth && !f.has_nulls && (f.type == PA_BIGINT || f.type == PA_INTEGER || f.type == PA_DATE);
-            if (!f.varwidth && !f.has_nulls && !getenv("PRESTO_AMD_SORT_NO_PAYLOAD")) {
-                for (size_t j = 0; j < outs.size() && payload.count < PA_SORT_MAX_PAYLOAD; j++) {
-                    const OutColumn& a = store_.cols[(size_t)outs[j]];
-                    const int w = a.varwidth ? 0 : type_width(a.type);
-                    if (a.has_nulls || (w != 4 && w != 8)) continue;
-                    if (outs[j] == sort_channels_[0] && images_serve) continue;   // (written from the sorted images)
-                    payload_of[j] = payload.count;
-                    payload.in[payload.count] = a.values.ptr();
-                    payload.out[payload.count] = payload_out_[payload.count].ensure((size_t)n * w);
-                    payload.width[payload.count] = w;
-                    payload.count++;
-                }
-            }
-        }
-        bool payload_moved = false;
-        const size_t sort_temp_bytes = sort_pairs_temp_bytes(n, payload.count);
-        void* sort_temp = radix_temp_.ensure(sort_temp_bytes);
-        uint64_t* or_and = static_cast<uint64_t*>(or_and_.ensure(key_or_and_bytes()));
-        std::vector<uint64_t> h_or_and(key_or_and_bytes() / 8);
-        const uint64_t* sorted_images = nullptr;  // the images of the channel sorted by last, in their sorted order (valid until perm changes again)
-        // pairs: OR / AND of the images already in or_and (the image kernel left them there), 0 = still to be computed
-        // crowded: images of doubles (exponent bits) or text crowd under few bit prefixes -- the sort takes its bucket bounds from a sample
-        auto sort_by_image = [&](int pairs, bool last, bool crowded) {
-            const uint64_t* in = keys;
-            if (!identity) {
-                launch_gather_flat(keys, 8, perm, n, kp[0], s);
-                in = kp[0];
-            }
-            const int blocks = pairs > 0 ? pairs : launch_key_or_and(in, n, or_and, s);
-            read_back(h_or_and.data(), or_and, (size_t)blocks * 16, s);
-            uint64_t h[2] = {0ULL, ~0ULL};
-            for (int b = 0; b < blocks; b++) {
-                h[0] |= h_or_and[2 * (size_t)b];
-                h[1] &= h_or_and[2 * (size_t)b + 1];
-            }
-            const uint64_t varying = h[0] ^ h[1];
-            sorted_images = nullptr;
-            if (varying == 0ULL) return;  // every image the same: the order stays
-            int begin_bit = __builtin_ctzll(varying);
-            const int end_bit = 64 - __builtin_clzll(varying);
-            // (rocPRIM 4.0's merge-sort path for small inputs builds its mask of the bit range with 1 << end_bit: a range that ends at
-            // bit 64 without starting at bit 0 compares nothing -- such ranges are widened to the whole key)
-            if (end_bit == 64) begin_bit = 0;
-            const bool carry = last && identity && payload.count > 0;
-            const int path = launch_sort_pairs(in, identity ? nullptr : perm, pos, kp[1], next, n, begin_bit, end_bit, sort_temp, sort_temp_bytes, s,
-                                               carry ? &payload : nullptr, crowded ? PA_SORT_HINT_CROWDED : PA_SORT_HINT_SPREAD);
-            payload_moved = carry && path == PA_SORT_BUCKETS;
-            timer.set_name(path == PA_SORT_LIBRARY ? "rocprim_radix_sort_pairs" : "pa_sort_buckets");   // (pa_op_kernel_name: which sort the last image took)
-            std::swap(perm, next);
-            identity = false;
-            sorted_images = kp[1];
-        };
-        for (int i = (int)sort_channels_.size() - 1; i >= 0; i--) {
-            const OutColumn& a = store_.cols[(size_t)sort_channels_[i]];
-            const int order = sort_orders_[i];
-            const bool descending = order >= 2, nulls_first = (order & 1) == 0;
-            const uint8_t* nulls = a.has_nulls ? a.nulls.as<uint8_t>() : nullptr;
-            if (a.varwidth) {
-                // least significant first: the length, then the 8-byte chunks from the last to the first
-                const int32_t max_len = varchar_max_length(a.offsets.as<int32_t>(), n, counts, s);
-                const int chunks = (max_len + 7) / 8;
-                for (int chunk = chunks; chunk >= 0; chunk--) {
-                    launch_varchar_chunk_keys(a.values.ptr(), a.offsets.as<int32_t>(), nulls, n, chunk == chunks ? -1 : chunk, descending ? 1 : 0, keys, s);
-                    sort_by_image(0, false, chunk != chunks);   // (the length key spreads; the byte chunks do not)
-                }
-            }
-            else {
-                // value image; NULL rows get one constant image (they keep arrival order among themselves) and their place
-                // relative to the values is decided by the separate NULL digit below
-                const int pairs = launch_topn_keys_or_and(a.type, a.values.ptr(), nullptr, nulls, n, descending ? PA_DESC_NULLS_LAST : PA_ASC_NULLS_LAST, keys, or_and, s);
-                sort_by_image(pairs, i == 0 && nulls == nullptr, a.type == PA_DOUBLE || a.type == PA_REAL);
-            }
-            if (nulls) {
-                materialize();
-                launch_sort_null_digits(nulls, perm, n, nulls_first ? 1 : 0, digits, s);
-                pass(2);
-                sorted_images = nullptr;
-            }
-        }
-        materialize();   // (no sort ran: every image the same)
-        timer.end(s);
-        // Output channels in sorted order (PagesIndex.appendTo).  Two kinds of channel are not gathered: one the sort brought along, and
-        // the first sort channel as an output channel, whose sorted images ARE the column (integers without NULL rows).
+        SortCarry carry;
+        memset(&carry.payload, 0, sizeof carry.payload);
         const int first_channel = sort_channels_[0];
-        {
-            const OutColumn& f = store_.cols[(size_t)first_channel];
-            if (f.varwidth || f.has_nulls || !(f.type == PA_BIGINT || f.type == PA_INTEGER || f.type == PA_DATE)) sorted_images = nullptr;
+        const OutColumn& f = store_.cols[(size_t)first_channel];
+        // (integers without NULL rows: the sorted images ARE the column)
+        const bool images_serve = !f.varwidth && !f.has_nulls && (f.type == PA_BIGINT || f.type == PA_INTEGER || f.type == PA_DATE);
+        if (!f.varwidth && !f.has_nulls && !getenv("PRESTO_AMD_SORT_NO_PAYLOAD")) {
+            SortPayload& payload = carry.payload;
+            for (size_t j = 0; j < outs.size() && payload.count < PA_SORT_MAX_PAYLOAD; j++) {
+                const OutColumn& a = store_.cols[(size_t)outs[j]];
+                const int w = a.varwidth ? 0 : type_width(a.type);
+                if (a.has_nulls || (w != 4 && w != 8)) continue;
+                if (outs[j] == first_channel && images_serve) continue;   // (written from the sorted images)
+                payload_of[j] = payload.count;
+                payload.in[payload.count] = a.values.ptr();
+                payload.out[payload.count] = payload_out_[payload.count].ensure((size_t)n * w);
+                payload.width[payload.count] = w;
+                payload.count++;
+            }
         }
+        std::vector<DevColumn> sort_cols;
+        for (int c : sort_channels_) sort_cols.push_back(store_.view(c));
+        timer.begin(s);
+        const int32_t* perm = sorter_.sort(sort_cols, sort_orders_, nullptr, 0, n, s, &carry);
+        timer.end(s);
+        // (pa_op_kernel_name: which sort the last image took)
+        if (carry.path != PA_SORT_NONE) timer.set_name(carry.path == PA_SORT_LIBRARY ? "rocprim_radix_sort_pairs" : "pa_sort_buckets");
+        // Output channels in sorted order (PagesIndex.appendTo).  Two kinds of channel are not gathered: one the sort brought along, and
+        // the first sort channel as an output channel, when its sorted images serve and the sorter still has them.
+        const uint64_t* sorted_images = images_serve ? carry.sorted_images : nullptr;
         out_cols_.clear();
         out_cols_.resize(outs.size());
         std::vector<bool> produced(outs.size(), false);
         for (size_t j = 0; j < outs.size(); j++) {
             const OutColumn& a = store_.cols[(size_t)outs[j]];
             if (a.varwidth) continue;
-            if (payload_moved && payload_of[j] >= 0) out_cols_[j].values = std::move(payload_out_[payload_of[j]]);
+            if (carry.moved && payload_of[j] >= 0) out_cols_[j].values = std::move(payload_out_[payload_of[j]]);
             else if (sorted_images != nullptr && outs[j] == first_channel)
                 launch_topn_values_of_keys(a.type, sorted_images, n, sort_orders_[0] >= 2, out_cols_[j].values.ensure((size_t)n * type_width(a.type)), s);
             else continue;
             produced[j] = true;
         }
-        store_.gather_sorted(perm, n, outs, &produced, out_cols_, scan_temp_, reinterpret_cast<int32_t*>(counts), s);
+        store_.gather_sorted(perm, n, outs, &produced, out_cols_, scan_temp_, static_cast<int32_t*>(total_word_.ensure(4)), s);
         publish_output(out_cols_, (int32_t)n, output_mem_, s, out, out_storage_);
         return true;
     }
@@ -347,8 +251,8 @@ private:
     std::vector<Held> held_;
     int32_t output_mem_ = PA_MEM_HOST;
     bool finishing_ = false, output_done_ = false;
-    DevBuf payload_out_[PA_SORT_MAX_PAYLOAD];
-    DevBuf perm_[2], digits_, pos_, counts_, keys_, part_temp_, scan_temp_, pair_keys_[2], radix_temp_, or_and_;
+    RowSorter sorter_;
+    DevBuf payload_out_[PA_SORT_MAX_PAYLOAD], scan_temp_, total_word_;   // (total_word_: gather_sorted's VARCHAR byte total)
     std::vector<OutColumn> out_cols_;
     std::vector<pa_column> out_storage_;
 };

@@ -161,3 +161,103 @@ def test_device_pages_that_stay_are_kept_not_copied(gpu, oracle, mix):
     assert norm(got) == norm(want)
     handed = sum(1 for p in pages if getattr(p, "on_release", None) is not None)
     assert sorted(released) == sorted(set(released)) and len(released) == handed, (released, handed)
+
+
+# ---- the seams between the row sorter and the operator: what rides, what is written from the images, what is gathered ------------------------
+ORDERS = {"asc_nulls_first": abi.ASC_NULLS_FIRST, "asc_nulls_last": abi.ASC_NULLS_LAST, "desc_nulls_first": abi.DESC_NULLS_FIRST,
+          "desc_nulls_last": abi.DESC_NULLS_LAST}
+SEAM_WORDS = [b"", b"a", b"ab", b"abc", b"abcdefgh", b"abcdefghi", b"abcdefghij", b"abcdefgh\x00", b"abd", b"b", b"ba", b"abcdefghabcdefghZ"]
+# case -> (sort channels, sort orders); channels: 0 BIGINT k, 1 INTEGER arrival index, 2 DOUBLE, 3 nullable BIGINT, 4 the case's extra channel
+SEAM_CASES = {
+    "a_trailing_constant": ([0, 4], [abi.ASC_NULLS_LAST, abi.ASC_NULLS_LAST]),
+    "b_trailing_three_values": ([0, 4], [abi.ASC_NULLS_LAST, abi.DESC_NULLS_LAST]),
+    "c_nullable_key_asc_nulls_first": ([0], [abi.ASC_NULLS_FIRST]),
+    "c_nullable_key_asc_nulls_last": ([0], [abi.ASC_NULLS_LAST]),
+    "c_nullable_key_desc_nulls_first": ([0], [abi.DESC_NULLS_FIRST]),
+    "c_nullable_key_desc_nulls_last": ([0], [abi.DESC_NULLS_LAST]),
+    "d_constant_key": ([0], [abi.ASC_NULLS_LAST]),
+    "e_double_key": ([2], [abi.DESC_NULLS_LAST]),
+    "f_varchar_first": ([4, 0], [abi.ASC_NULLS_LAST, abi.DESC_NULLS_LAST]),
+}
+
+
+def seam_page(case, n):
+    """The four channels every case outputs, and the case's own fifth.  From two rows on, k and the DOUBLE take at least two values (rows
+    0 and 1 differ), so a sort by them runs; both have ties; the DOUBLE has no NaN and no -0.0 (Python's == would tie it with +0.0).  k
+    spreads over ten bits, so beyond one LDS bucket its sort is the partition passes + bucket sort too, not the library's."""
+    rng = np.random.default_rng(n * 31 + len(case))
+    k = rng.integers(0, 1024, n)
+    k[:2] = [7, 3][:n]
+    k_nulls = None
+    if case.startswith("c_"):
+        k_nulls = rng.random(n) < 0.1
+        k_nulls[:2] = [False, False][:n]
+        k_nulls[-1] = n <= 2 or k_nulls[-1]   # (the small pages have a NULL row too)
+    elif case.startswith("d_"):
+        k[:] = 42
+    d = rng.integers(-40, 40, n) / 8.0
+    d[:2] = [1.5, -2.25][:n]
+    blocks = [Block.bigint(k, k_nulls), Block.integer(np.arange(n, dtype=np.int32)), Block.double(d), Block.bigint(rng.integers(-9, 9, n), rng.random(n) < 0.2)]
+    types = [abi.BIGINT, abi.INTEGER, abi.DOUBLE, abi.BIGINT]
+    if case.startswith("a_"):
+        blocks.append(Block.integer(np.full(n, 5, dtype=np.int32)))
+    elif case.startswith("b_"):
+        blocks.append(Block.integer(rng.integers(0, 3, n).astype(np.int32)))
+    elif case.startswith("f_"):
+        blocks.append(Block.varchar([SEAM_WORDS[j] for j in rng.integers(0, len(SEAM_WORDS), n)]))
+    if len(blocks) == 5:
+        types.append(blocks[4].type)
+    return types, Page(blocks, n)
+
+
+def model_order(rows, channels, orders):
+    """Python's stable sorted(), channel by channel from the last to the first: by value (reversed for DESC; reverse keeps ties in order), then by
+    the NULL rank alone -- together the key (NULL rank, value) of the channel.  A VARCHAR compares as bytes."""
+    for c, order in reversed(list(zip(channels, orders))):
+        zero = b"" if any(isinstance(r[c], bytes) for r in rows) else 0
+        rows = sorted(rows, key=lambda r: zero if r[c] is None else r[c], reverse=order in (abi.DESC_NULLS_FIRST, abi.DESC_NULLS_LAST))
+        nulls_first = order in (abi.ASC_NULLS_FIRST, abi.DESC_NULLS_FIRST)
+        rows = sorted(rows, key=lambda r: (r[c] is None) != nulls_first)
+    return rows
+
+
+@pytest.mark.parametrize("n", [1, 2, 300, 2049, 4097])   # (one LDS bucket ends at 2048; 4097: a partition pass, a tile ending inside a bucket)
+@pytest.mark.parametrize("case", list(SEAM_CASES))
+def test_sorter_and_operator_seams(gpu, monkeypatch, case, n):
+    """What OrderBy adds to the shared row sort, against a model that knows nothing of it: (a) the sort channels behind the first all
+    constant -- the first channel's sort starts from the identity, the payload rides, k is written from the sorted images; (b) it does not
+    start from the identity -- nothing rides, k still comes from the images; (c) a NULL digit follows -- neither; (d) no sort runs at all --
+    arrival order; (e) a DOUBLE key -- the payload rides, the images do not serve; (f) a VARCHAR first channel -- neither.  Every case with
+    the input as one stable device page and as two host pages (one row: one page), with and without the riding payload."""
+    channels, orders = SEAM_CASES[case]
+    types, page = seam_page(case, n)
+    rows = page.to_rows()
+    expected = model_order(rows, channels, orders)
+    assert sorted(r[1] for r in expected) == list(range(n))
+    if case.startswith("d_"):
+        assert expected == rows
+    outs = list(range(len(types)))
+    k_values = {r[0] for r in rows if r[0] is not None}
+    results = []
+    for input_mem in ("stable_device_page", "two_host_pages"):
+        for no_payload in (False, True):
+            if no_payload:
+                monkeypatch.setenv("PRESTO_AMD_SORT_NO_PAYLOAD", "1")
+            else:
+                monkeypatch.delenv("PRESTO_AMD_SORT_NO_PAYLOAD", raising=False)
+            if input_mem == "stable_device_page":
+                dev = upload_page(page)
+                pages = [Page(dev.blocks, n, abi.MEM_DEVICE, stable=True)]
+            else:
+                half = (n + 1) // 2
+                pages = [page.get_region(0, half), page.get_region(half, n - half)]
+            op = OrderByOperator(types, outs, channels, orders)
+            got = rows_of(to_pages(op, pages))
+            # (a, b beyond one bucket too: k's own sort is the last one, and ten spread bits stay on the hand-written path; in c the constant
+            # image of the NULL rows widens the bit range, the keys crowd under few prefixes and the library may take over)
+            if len(k_values) > 1 and (n <= 2048 or case[0] in "ab"):
+                assert op.kernelName() == "pa_sort_buckets"
+            op.close()
+            results.append(got)
+    for got in results:
+        assert got == expected
