@@ -163,7 +163,23 @@ typedef enum pa_call_op {    /* operator / function of a CALL node; operand type
     PA_OP_EQUAL = 6, PA_OP_NOT_EQUAL = 7, PA_OP_LESS_THAN = 8, PA_OP_LESS_THAN_OR_EQUAL = 9,
     PA_OP_GREATER_THAN = 10, PA_OP_GREATER_THAN_OR_EQUAL = 11,
     PA_OP_NOT = 12,          /* $not */
-    PA_OP_CAST = 13          /* to node type; INTEGER/DATE->BIGINT, BIGINT/INTEGER->DOUBLE */
+    PA_OP_CAST = 13,         /* to node type; INTEGER/DATE->BIGINT, BIGINT/INTEGER->DOUBLE */
+    /* Scalar functions.  A NULL argument gives NULL; none of them raises per row.  Code points are counted by lead bytes: UTF-8 is
+     * never validated, a code point is as long as its lead byte says, clipped to the value's end (the reference's behaviour on malformed
+     * input -- NonStrictUTF8Encoding, airlift's unchecked stepping -- is not restated). */
+    PA_OP_LIKE = 14,         /* (value VARCHAR, pattern VARCHAR CONSTANT[, escape VARCHAR CONSTANT]) -> BOOLEAN.  TM/type/LikeFunctions.java:74-89
+                              * likeVarchar, :198-241 likePattern, :181-195 / :244-255 the escape: the whole value must match; % = any run of bytes,
+                              * _ = one code point (line feed included), every other character itself; an empty escape disables escaping, a
+                              * non-empty one is one BMP character followed by %, _ or itself -- otherwise PA_ERR_INVALID_ARGUMENT when the
+                              * expression is generated.  A NULL pattern / escape constant: constant NULL.  A pattern / escape that is no
+                              * CONSTANT node: PA_ERR_NOT_SUPPORTED.  A line feed before the end of the value: DESIGN.md section 5. */
+    PA_OP_SUBSTR = 15,       /* (value VARCHAR, start BIGINT[, length BIGINT]) -> VARCHAR, a slice of the argument.  TM/operator/scalar/
+                              * StringFunctions.java:278-310, :325-368: code points, 1-based; start 0, an empty value or length <= 0 give '';
+                              * start / length saturate to int32; a negative start counts from the end; the int addition of :360 wraps */
+    PA_OP_LENGTH = 16,       /* (value VARCHAR) -> BIGINT: code points = bytes that are not 10xxxxxx.  StringFunctions.java:98-101 */
+    PA_OP_YEAR = 17,         /* (DATE) -> BIGINT.  TM/operator/scalar/DateTimeFunctions.java:501 yearFromDate: proleptic Gregorian, year 0 exists */
+    PA_OP_MONTH = 18,        /* DateTimeFunctions.java:477 monthFromDate */
+    PA_OP_DAY = 19           /* DateTimeFunctions.java:428 dayFromDate */
 } pa_call_op;
 
 typedef enum pa_special_form {

@@ -188,6 +188,26 @@ inline Expr specialForm(int32_t form, int32_t type, std::vector<Expr> args)
     e->arguments = std::move(args);
     return e;
 }
+inline Expr constantVarchar(const std::string& bytes)
+{
+    auto e = std::make_shared<RowExpression>();
+    e->node.kind = PA_EXPR_CONSTANT;
+    e->node.type = PA_VARCHAR;
+    e->text = bytes;
+    return e;
+}
+// the scalar functions of pa_call_op (PA_OP_LIKE .. PA_OP_DAY): pattern and escape are constants
+inline Expr like(Expr value, const std::string& pattern) { return call(PA_OP_LIKE, PA_BOOLEAN, {std::move(value), constantVarchar(pattern)}); }
+inline Expr like(Expr value, const std::string& pattern, const std::string& escape)
+{
+    return call(PA_OP_LIKE, PA_BOOLEAN, {std::move(value), constantVarchar(pattern), constantVarchar(escape)});
+}
+inline Expr substr(Expr value, Expr start) { return call(PA_OP_SUBSTR, PA_VARCHAR, {std::move(value), std::move(start)}); }
+inline Expr substr(Expr value, Expr start, Expr length) { return call(PA_OP_SUBSTR, PA_VARCHAR, {std::move(value), std::move(start), std::move(length)}); }
+inline Expr length(Expr value) { return call(PA_OP_LENGTH, PA_BIGINT, {std::move(value)}); }
+inline Expr year(Expr date) { return call(PA_OP_YEAR, PA_BIGINT, {std::move(date)}); }
+inline Expr month(Expr date) { return call(PA_OP_MONTH, PA_BIGINT, {std::move(date)}); }
+inline Expr day(Expr date) { return call(PA_OP_DAY, PA_BIGINT, {std::move(date)}); }
 
 // children-first flattening into pa_expr (what the Java RowExpressionVisitor of INTEGRATION.md emits)
 class SerializedExpression {

@@ -41,6 +41,8 @@ final class RowExpressionSerializer
     // pa_type / pa_expr_kind / pa_call_op / pa_special_form ordinals
     static final int PA_BIGINT = 0, PA_INTEGER = 1, PA_DATE = 2, PA_DOUBLE = 3, PA_BOOLEAN = 4, PA_VARCHAR = 5, PA_REAL = 7, PA_DECIMAL = 8, PA_LONG_DECIMAL = 9;
     private static final int INPUT_REF = 0, CONSTANT = 1, CALL = 2, SPECIAL = 3;
+    // scalar functions (pa_call_op behind PA_OP_CAST = 13)
+    static final int OP_LIKE = 14, OP_SUBSTR = 15, OP_LENGTH = 16, OP_YEAR = 17, OP_MONTH = 18, OP_DAY = 19;
 
     private final List<int[]> nodes = new ArrayList<>();      // kind, op, type, typeParam, channel, isNull, nargs, firstArg
     private final List<Long> longs = new ArrayList<>();
@@ -144,10 +146,60 @@ final class RowExpressionSerializer
             case "$operator$less_than_or_equal": op = 9; break;
             case "$not": op = 12; break;
             case "$operator$cast": op = 13; break;
+            case "like": return like(call);
+            case "substr":
+            case "substring":
+                requireArgument(call, 0, PA_VARCHAR);   // (a char(x) value is no VarcharType: typeOf refuses it)
+                op = OP_SUBSTR;
+                break;
+            case "length":
+                requireArgument(call, 0, PA_VARCHAR);
+                op = OP_LENGTH;
+                break;
+            case "year":
+            case "month":
+            case "day":
+                requireArgument(call, 0, PA_DATE);      // (the timestamp and interval variants stay with the reference)
+                op = name.equals("year") ? OP_YEAR : (name.equals("month") ? OP_MONTH : OP_DAY);
+                break;
             default: throw new UnsupportedOnDevice("function " + name);
         }
         // (>, >=, <> reach the RowExpression level as swapped / negated forms of the three comparison operators above)
         return add(CALL, op, call.getType(), 0, false, children(call.getArguments()), 0, 0, null);
+    }
+
+    private static void requireArgument(CallExpression call, int index, int type)
+    {
+        if (call.getArguments().size() <= index || typeOf(call.getArguments().get(index).getType()) != type) {
+            throw new UnsupportedOnDevice("function " + call.getResolvedFunction().getSignature().getName() + " over " + call.getArguments());
+        }
+    }
+
+    /**
+     * like(value, $like_pattern(pattern[, escape])) becomes PA_OP_LIKE(value, pattern[, escape]) when pattern and escape are varchar
+     * constants (LikeFunctions.java:91-118).  A pattern the optimizer has already folded into a LikePatternType constant (a compiled
+     * JoniRegexp) is left unmapped: the planner keeps the reference operator (INTEGRATION.md).
+     */
+    private Integer like(CallExpression call)
+    {
+        List<RowExpression> arguments = call.getArguments();
+        if (arguments.size() != 2 || !(arguments.get(1) instanceof CallExpression)) {
+            throw new UnsupportedOnDevice("like with a folded or non-constant pattern");
+        }
+        CallExpression pattern = (CallExpression) arguments.get(1);
+        if (!pattern.getResolvedFunction().getSignature().getName().equals("$like_pattern") || pattern.getArguments().isEmpty() || pattern.getArguments().size() > 2) {
+            throw new UnsupportedOnDevice("like pattern " + pattern);
+        }
+        requireArgument(call, 0, PA_VARCHAR);
+        List<Integer> ids = new ArrayList<>();
+        ids.add(arguments.get(0).accept(this, null));
+        for (RowExpression argument : pattern.getArguments()) {
+            if (!(argument instanceof ConstantExpression) || typeOf(argument.getType()) != PA_VARCHAR) {
+                throw new UnsupportedOnDevice("like pattern / escape that is no varchar constant");
+            }
+            ids.add(argument.accept(this, null));
+        }
+        return add(CALL, OP_LIKE, call.getType(), 0, false, ids, 0, 0, null);
     }
 
     @Override

@@ -66,7 +66,8 @@ MEM_HOST, MEM_DEVICE = 0, 1
 EXPR_INPUT_REF, EXPR_CONSTANT, EXPR_CALL, EXPR_SPECIAL = range(4)
 # pa_call_op
 (OP_ADD, OP_SUBTRACT, OP_MULTIPLY, OP_DIVIDE, OP_MODULUS, OP_NEGATE, OP_EQUAL, OP_NOT_EQUAL, OP_LESS_THAN,
- OP_LESS_THAN_OR_EQUAL, OP_GREATER_THAN, OP_GREATER_THAN_OR_EQUAL, OP_NOT, OP_CAST) = range(14)
+ OP_LESS_THAN_OR_EQUAL, OP_GREATER_THAN, OP_GREATER_THAN_OR_EQUAL, OP_NOT, OP_CAST,
+ OP_LIKE, OP_SUBSTR, OP_LENGTH, OP_YEAR, OP_MONTH, OP_DAY) = range(20)
 # pa_special_form
 FORM_AND, FORM_OR, FORM_BETWEEN, FORM_IS_NULL, FORM_IF, FORM_COALESCE, FORM_IN = range(7)
 # pa_agg_fn

@@ -3,6 +3,7 @@
 
 #include "exprgen.hpp"
 
+#include <algorithm>
 #include <cinttypes>
 #include <cmath>
 
@@ -197,6 +198,135 @@ GenValue RowCodegen::emit_compare(int32_t op, const GenValue& a, const GenValue&
     return r;
 }
 
+// ---- LIKE: the constant pattern decides the code (LikeFunctions.java:198-241; escape :181-195, :244-255) ----
+namespace {
+struct LikeToken {
+    int kind;          // 0 literal, 1 `%`, 2 `_`
+    std::string lit;
+};
+
+size_t utf8_length(const std::string& s, size_t at)
+{
+    const unsigned char c = (unsigned char)s[at];
+    const size_t n = c < 0xC0 ? 1 : (c < 0xE0 ? 2 : (c < 0xF0 ? 3 : 4));
+    return std::min(n, s.size() - at);
+}
+
+// the pattern as tokens: neighbouring literal characters joined, runs of `%` collapsed
+std::vector<LikeToken> like_tokens(const std::string& pattern, bool has_escape, const std::string& escape)
+{
+    static const char* bad = "Escape character must be followed by '%', '_' or the escape character itself";
+    bool escaping = has_escape && !escape.empty();   // an empty escape string disables escaping (:247-250)
+    if (escaping) {
+        // one BMP character: one code point of at most 3 bytes
+        PA_REQUIRE(utf8_length(escape, 0) == escape.size() && escape.size() <= 3 && ((unsigned char)escape[0] < 0x80 || (unsigned char)escape[0] >= 0xC0),
+                   PA_ERR_INVALID_ARGUMENT, "Escape string must be a single character");
+    }
+    std::vector<LikeToken> tokens;
+    auto literal = [&](const std::string& bytes) {
+        if (tokens.empty() || tokens.back().kind != 0) tokens.push_back({0, ""});
+        tokens.back().lit += bytes;
+    };
+    bool escaped = false;
+    for (size_t at = 0; at < pattern.size();) {
+        const std::string c = pattern.substr(at, utf8_length(pattern, at));
+        at += c.size();
+        const bool is_escape = escaping && c == escape;
+        PA_REQUIRE(!escaped || c == "%" || c == "_" || is_escape, PA_ERR_INVALID_ARGUMENT, bad);
+        if (is_escape && !escaped) {
+            escaped = true;
+            continue;
+        }
+        if (c == "%" && !escaped) {
+            if (tokens.empty() || tokens.back().kind != 1) tokens.push_back({1, ""});
+        }
+        else if (c == "_" && !escaped) tokens.push_back({2, ""});
+        else literal(c);
+        escaped = false;
+    }
+    PA_REQUIRE(!escaped, PA_ERR_INVALID_ARGUMENT, bad);
+    return tokens;
+}
+}  // namespace
+
+GenValue RowCodegen::emit_like(const OwnedExpr& e, int32_t id, std::ostringstream& out)
+{
+    const pa_expr_node& n = e.node(id);
+    const int32_t* a = e.node_args(id);
+    PA_REQUIRE(n.nargs == 2 || n.nargs == 3, PA_ERR_INVALID_ARGUMENT, "LIKE needs a value, a pattern and at most an escape");
+    GenValue x = emit_node(e, a[0], out);
+    PA_REQUIRE(x.type == PA_VARCHAR, PA_ERR_INVALID_ARGUMENT, "LIKE needs a VARCHAR value");
+    bool null_constant = false;
+    for (int32_t k = 1; k < n.nargs; k++) {
+        const pa_expr_node& c = e.node(a[k]);
+        PA_REQUIRE(c.kind == PA_EXPR_CONSTANT, PA_ERR_NOT_SUPPORTED, "LIKE with a pattern or escape that is not a constant is not on the device path");
+        PA_REQUIRE(c.type == PA_VARCHAR, PA_ERR_INVALID_ARGUMENT, "LIKE needs a VARCHAR pattern and escape");
+        null_constant = null_constant || c.is_null;
+    }
+    GenValue r;
+    r.type = PA_BOOLEAN;
+    if (null_constant) {  // a NULL argument gives NULL
+        r.v = "false";
+        r.n = "true";
+        return r;
+    }
+    const std::vector<LikeToken> tokens = like_tokens(e.strings[a[1]], n.nargs == 3, n.nargs == 3 ? e.strings[a[2]] : std::string());
+    r.n = x.n;
+    r.v = fresh("t");
+    // the value of a NULL row is an unspecified pointer: guard the byte loops
+    const std::string guard = r.nullable() ? "(" + r.n + ") ? false : " : "";
+    auto lit = [](const std::string& s) { return bytes_literal(s) + ", " + std::to_string(s.size()); };
+    bool any_one = false;
+    for (const LikeToken& t : tokens) any_one = any_one || t.kind == 2;
+    if (any_one) {
+        // `_`: the general matcher over the compact pattern (kernels/pa_scalar.h)
+        std::string enc;
+        for (const LikeToken& t : tokens) {
+            for (unsigned char c : t.lit) PA_REQUIRE(c < 0xFE, PA_ERR_NOT_SUPPORTED, "LIKE with `_` over a pattern that is not UTF-8 is not on the device path");
+            enc += t.kind == 1 ? std::string(1, (char)0xFF) : (t.kind == 2 ? std::string(1, (char)0xFE) : t.lit);
+        }
+        out << "const bool " << r.v << " = " << guard << "pa_like_general(" << x.v << ", " << x.len << ", " << lit(enc) << ");\n";
+        return r;
+    }
+    // no `_`: the literals between the `%`.  parts[0] is anchored at the start, the last part at the end, the parts between them are
+    // found leftmost one after another in what the two leave (exact for `%`)
+    std::vector<std::string> parts(1);
+    for (const LikeToken& t : tokens) {
+        if (t.kind == 1) parts.emplace_back();
+        else parts.back() = t.lit;
+    }
+    if (parts.size() == 1) {
+        out << "const bool " << r.v << " = " << guard << "pa_str_eq(" << x.v << ", " << x.len << ", " << lit(parts[0]) << ");\n";
+        return r;
+    }
+    const std::string &head = parts.front(), &tail = parts.back();
+    std::vector<std::string> ends;
+    // both ends anchored: they must not overlap ('ab%ba' does not match 'aba')
+    if (!head.empty() && !tail.empty()) ends.push_back(x.len + " >= " + std::to_string(head.size() + tail.size()));
+    if (!head.empty()) ends.push_back("pa_str_prefix(" + x.v + ", " + x.len + ", " + lit(head) + ")");
+    if (!tail.empty()) ends.push_back("pa_str_suffix(" + x.v + ", " + x.len + ", " + lit(tail) + ")");
+    std::string anchored;
+    for (size_t k = 0; k < ends.size(); k++) anchored += (k ? " && " : "") + ends[k];
+    const std::vector<std::string> middles(parts.begin() + 1, parts.end() - 1);
+    if (middles.empty()) {
+        out << "const bool " << r.v << " = " << guard << "(" << (anchored.empty() ? "true" : anchored) << ");\n";
+        return r;
+    }
+    if (middles.size() == 1 && anchored.empty()) {  // %lit%: one forward search
+        out << "const bool " << r.v << " = " << guard << "(pa_str_find(" << x.v << ", 0, " << x.len << ", " << lit(middles[0]) << ") >= 0);\n";
+        return r;
+    }
+    const std::string at = fresh("t");
+    out << "bool " << r.v << " = " << guard << "(" << (anchored.empty() ? "true" : anchored) << ");\n";
+    out << "{ i32 " << at << " = " << head.size() << "; const i32 " << at << "e = " << x.len << " - " << tail.size() << ";\n";
+    for (const std::string& m : middles) {
+        out << "if (" << r.v << ") { " << at << " = pa_str_find(" << x.v << ", " << at << ", " << at << "e, " << lit(m) << "); " << r.v << " = " << at
+            << " >= 0; " << at << " += " << m.size() << "; }\n";
+    }
+    out << "}\n";
+    return r;
+}
+
 GenValue RowCodegen::emit_node(const OwnedExpr& e, int32_t id, std::ostringstream& out)
 {
     const pa_expr_node& n = e.node(id);
@@ -297,6 +427,49 @@ GenValue RowCodegen::emit_node(const OwnedExpr& e, int32_t id, std::ostringstrea
                 else if (n.type == PA_BIGINT && is_int_type(x.type)) r.v = x.v;
                 else if (n.type == x.type) { r.v = x.v; r.len = x.len; }
                 else throw Error(PA_ERR_NOT_SUPPORTED, "CAST not supported on device");
+                return r;
+            }
+            if (n.op == PA_OP_LIKE) return emit_like(e, id, out);
+            if (n.op == PA_OP_SUBSTR) {
+                PA_REQUIRE(n.nargs == 2 || n.nargs == 3, PA_ERR_INVALID_ARGUMENT, "substr needs 2 or 3 arguments");
+                PA_REQUIRE(n.type == PA_VARCHAR, PA_ERR_INVALID_ARGUMENT, "substr gives a VARCHAR");
+                GenValue x = emit_node(e, a[0], out);
+                PA_REQUIRE(x.type == PA_VARCHAR, PA_ERR_INVALID_ARGUMENT, "substr needs a VARCHAR value");
+                GenValue pos[2];
+                for (int32_t k = 1; k < n.nargs; k++) {
+                    pos[k - 1] = emit_node(e, a[k], out);
+                    PA_REQUIRE(pos[k - 1].type != PA_INTEGER, PA_ERR_NOT_SUPPORTED, "substr with an INTEGER start / length needs an explicit CAST");
+                    PA_REQUIRE(pos[k - 1].type == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "substr needs a BIGINT start / length");
+                }
+                const bool has_length = n.nargs == 3;
+                r.n = or_nulls({x.n, pos[0].n, has_length ? pos[1].n : std::string("false")});
+                r.v = fresh("t");
+                r.len = r.v + "l";
+                // StringFunctions.java:278-310 / :325-368: a slice of the argument, no bytes are copied
+                out << "i32 " << r.v << "f = 0; const i32 " << r.len << " = " << (r.nullable() ? "(" + r.n + ") ? 0 : " : "") << "pa_substr(" << x.v << ", "
+                    << x.len << ", " << pos[0].v << ", " << (has_length ? "true, " + pos[1].v : std::string("false, 0LL")) << ", &" << r.v << "f);\n";
+                out << "const u8* const " << r.v << " = " << x.v << " + " << r.v << "f;\n";
+                return r;
+            }
+            if (n.op == PA_OP_LENGTH) {
+                PA_REQUIRE(n.nargs == 1, PA_ERR_INVALID_ARGUMENT, "length needs 1 argument");
+                PA_REQUIRE(n.type == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "length gives a BIGINT");
+                GenValue x = emit_node(e, a[0], out);
+                PA_REQUIRE(x.type == PA_VARCHAR, PA_ERR_INVALID_ARGUMENT, "length needs a VARCHAR argument");
+                r.n = x.n;
+                r.v = fresh("t");
+                out << "const i64 " << r.v << " = " << (r.nullable() ? "(" + r.n + ") ? 0LL : " : "") << "(i64)pa_cp_count(" << x.v << ", " << x.len << ");\n";
+                return r;
+            }
+            if (n.op == PA_OP_YEAR || n.op == PA_OP_MONTH || n.op == PA_OP_DAY) {
+                PA_REQUIRE(n.nargs == 1, PA_ERR_INVALID_ARGUMENT, "year / month / day need 1 argument");
+                PA_REQUIRE(n.type == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "year / month / day give a BIGINT");
+                GenValue x = emit_node(e, a[0], out);
+                PA_REQUIRE(x.type == PA_DATE, PA_ERR_INVALID_ARGUMENT, "year / month / day need a DATE argument");
+                r.n = x.n;
+                r.v = fresh("t");
+                out << "const i64 " << r.v << " = " << (r.nullable() ? "(" + r.n + ") ? 0LL : " : "") << "pa_civil_from_days(" << x.v << ", "
+                    << (n.op - PA_OP_YEAR) << ");\n";
                 return r;
             }
             PA_REQUIRE(n.op >= PA_OP_ADD && n.op <= PA_OP_NEGATE, PA_ERR_NOT_SUPPORTED, "unknown call operator");

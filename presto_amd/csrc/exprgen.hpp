@@ -63,6 +63,7 @@ public:
 private:
     GenValue emit_node(const OwnedExpr& e, int32_t id, std::ostringstream& out);
     GenValue emit_compare(int32_t op, const GenValue& a, const GenValue& b, std::ostringstream& out);
+    GenValue emit_like(const OwnedExpr& e, int32_t id, std::ostringstream& out);
     std::string fresh(const char* prefix);
     static std::string or_nulls(const std::vector<std::string>& ns);
 

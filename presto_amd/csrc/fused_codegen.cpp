@@ -79,7 +79,7 @@ KernelInfo FusedGen::run()
     ri.short_bound = s.short_bound;
     if (staged) {
         std::vector<VectorVar> vars;
-        PA_REQUIRE(vector_load_vars(ri, layout, vars), PA_ERR_NOT_SUPPORTED, "no staged variant for these column types");
+        PA_REQUIRE(vector_load_vars(ri, layout, vars, ColumnNames(), true), PA_ERR_NOT_SUPPORTED, "no staged variant for these column types");
     }
     brow = variant == V_BROW;
     lds_table = variant == V_LDSH || variant == V_LDSP;

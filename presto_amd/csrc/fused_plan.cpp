@@ -219,6 +219,9 @@ void finalize_spec(Spec& s)
     s.interned.assign(s.n_in, false);
     for (int j : s.group_proj) {
         const OwnedExpr& pe = s.proj[j];
+        // a computed string (substr) has no declared bound and no dictionary to intern it by
+        PA_REQUIRE(pe.root_type() != PA_VARCHAR || pe.node(pe.root).kind != PA_EXPR_CALL || pe.node(pe.root).op != PA_OP_SUBSTR, PA_ERR_NOT_SUPPORTED,
+                   "VARCHAR expressions as group keys are not on the device path");
         if (pe.is_input_ref() && pe.root_type() == PA_VARCHAR) {
             int c = pe.node(pe.root).channel;
             if (s.in_params[c] >= 1 && s.in_params[c] <= 7) s.short_bound[c] = s.in_params[c];

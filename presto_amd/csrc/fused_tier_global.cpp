@@ -119,7 +119,7 @@ void FusedGen::staged_page_loop()
 {
     const int S = s.n_stages;
     std::vector<VectorVar> vars;
-    vector_load_vars(ri, layout, vars);
+    vector_load_vars(ri, layout, vars, ColumnNames(), true);
     // per channel: the last stage that reads it (the projections': the last stage)
     std::vector<int> last(s.n_in, -1);
     for (int k = 0; k < S; k++) {
@@ -171,6 +171,7 @@ void FusedGen::staged_page_loop()
                 case PA_REAL: a += ", 0.0f"; break;
                 case PA_DOUBLE: a += ", 0.0"; break;
                 case PA_BOOLEAN: a += ", false"; break;
+                case PA_VARCHAR: a += ", (const u8*)0, 0"; break;
                 default: a += ", (i64)0"; break;
             }
             if (layout[c].nullable) a += ", false";
@@ -183,8 +184,8 @@ void FusedGen::staged_page_loop()
         std::string any;
         const int r0 = v.per_quad == 2 ? 2 * v.half : 0, r1 = v.per_quad == 2 ? r0 + 2 : 4;
         for (int r = r0; r < r1; r++) any += (any.empty() ? "" : " || ") + std::string("!") + H(h) + "d" + std::to_string(r);
-        const std::string idx = v.per_quad == 2 ? "2 * " + q + (v.half ? " + 1" : "") : q;
-        const std::string ld = "((const " + v.type + "*)" + v.array + ")[(" + any + ") ? " + idx + " : 0]";
+        const std::string idx = v.per_quad == 2 ? "2 * " + q + (v.half ? " + 1" : "") : (v.per_quad == 0 ? "4 * " + q + " + 4" : q);
+        const std::string ld = "((const " + v.type + "*)" + v.array + ")[(" + any + ") ? " + idx + " : " + (v.per_quad == 0 ? "4" : "0") + "]";
         return v.maybe_null ? "(" + v.array + " ? " + ld + " : 0u)" : ld;
     };
     for (int k = 1; k < S; k++) src << "    u32 pa_cnt" << k << " = 0u;\n";

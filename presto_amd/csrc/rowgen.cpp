@@ -178,12 +178,12 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
 
 std::string VectorVar::load(const std::string& q) const
 {
-    const std::string idx = per_quad == 2 ? "2 * (" + q + ")" + (half ? " + 1" : "") : "(" + q + ")";
+    const std::string idx = per_quad == 2 ? "2 * (" + q + ")" + (half ? " + 1" : "") : (per_quad == 0 ? "4 * (" + q + ") + 4" : "(" + q + ")");
     const std::string ld = "((const " + type + "*)" + array + ")[" + idx + "]";
     return maybe_null ? "(" + array + " ? " + ld + " : 0u)" : ld;
 }
 
-bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::vector<VectorVar>& vars, const ColumnNames& nm)
+bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::vector<VectorVar>& vars, const ColumnNames& nm, bool strings)
 {
     vars.clear();
     for (int c = 0; c < s.n_in; c++) {
@@ -204,6 +204,11 @@ bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layo
             case PA_DATE: vars.push_back(VectorVar{"pa_i32x4", "A" + C, nm.v(c), 1, 0, false}); break;
             case PA_REAL: vars.push_back(VectorVar{"pa_f32x4", "A" + C, nm.v(c), 1, 0, false}); break;
             case PA_BOOLEAN: vars.push_back(VectorVar{"u32", "A" + C, nm.v(c), 1, 0, false}); break;
+            case PA_VARCHAR:  // the quad's four offsets and its end: the bytes are the row function's to read
+                if (!strings || s.short_bound[c] > 0) return false;
+                vars.push_back(VectorVar{"pa_i32x4", "O" + C, nm.o(c), 1, 0, false});
+                vars.push_back(VectorVar{"i32", "E" + C, nm.o(c), 0, 0, false});
+                break;
             default: return false;
         }
         if (layout[c].nullable) vars.push_back(VectorVar{"u32", "N" + C, nm.nl(c), 1, 0, true});
@@ -235,6 +240,11 @@ std::string vector_var_channel_args(const std::vector<ChannelLayout>& layout, co
         case PA_DATE: a += ", (i64)" + P + "A" + C + "." + xyzw[r]; break;
         case PA_REAL: a += ", " + P + "A" + C + "." + xyzw[r]; break;
         case PA_BOOLEAN: a += ", ((" + P + "A" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u"; break;
+        case PA_VARCHAR: {
+            const std::string lo = P + "O" + C + "." + xyzw[r], hi = r < 3 ? P + "O" + C + "." + xyzw[r + 1] : P + "E" + C;
+            a += ", (const u8*)" + ColumnNames().v(c) + " + " + lo + ", " + hi + " - " + lo;
+            break;
+        }
         default: throw Error(PA_ERR_NOT_SUPPORTED, "column type not supported on device");
     }
     if (layout[c].nullable) a += ", ((" + P + "N" + C + " >> " + std::to_string(8 * r) + ") & 0xffu) != 0u";

@@ -46,13 +46,15 @@ void emit_vector_loads(const RowInputs& s, const std::vector<ChannelLayout>& lay
 // whose rows are still to be accumulated).  false: some used channel does not load that simply (VARCHAR, long DECIMAL).
 struct VectorVar {
     std::string type, name, array;   // load of quad q: ((const type*)array)[index(q)], guarded when the array may be null
-    int per_quad;                    // 2: the variable holds half a quad (index 2 q + half), 1: the whole quad
+    int per_quad;                    // 2: the variable holds half a quad (index 2 q + half), 1: the whole quad, 0: the i32 behind it (4 q + 4)
     int half;
     bool maybe_null;                 // (a valueIsNull array that a page may leave out)
     int channel = -1;
     std::string load(const std::string& q) const;
 };
-bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::vector<VectorVar>& vars, const ColumnNames& names = ColumnNames());
+// `strings`: VARCHAR channels load too, as their offsets (O<c>, E<c>; the argument lists then name the page's own buffers, a.v[c])
+bool vector_load_vars(const RowInputs& s, const std::vector<ChannelLayout>& layout, std::vector<VectorVar>& vars, const ColumnNames& names = ColumnNames(),
+                      bool strings = false);
 std::string vector_var_args(const RowInputs& s, const std::vector<ChannelLayout>& layout, const std::string& prefix, int r);
 // the part of that list that is channel c's
 std::string vector_var_channel_args(const std::vector<ChannelLayout>& layout, const std::string& prefix, int r, int c);

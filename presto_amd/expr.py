@@ -50,6 +50,14 @@ class RowExpression:
     def isin(self, *values): return special(abi.FORM_IN, abi.BOOLEAN, self, *[_lift(v, self.type) for v in values])
     def cast(self, type_): return call(abi.OP_CAST, type_, self)
 
+    def like(self, pattern, escape=None):
+        """value LIKE pattern [ESCAPE escape]: pattern and escape are constants (str / bytes, or a constant node; None inside a constant
+        node is the typed NULL)"""
+        args = [self, _lift(pattern, abi.VARCHAR)]
+        if escape is not None:
+            args.append(_lift(escape, abi.VARCHAR))
+        return call(abi.OP_LIKE, abi.BOOLEAN, *args)
+
 
 def decimal_result_type(op, a, b):
     """The result type the reference's signatures derive for decimal arithmetic (core/trino-main/src/main/java/io/trino/type/
@@ -94,6 +102,18 @@ def or_(*args): return special(abi.FORM_OR, abi.BOOLEAN, *args)
 def not_(a): return call(abi.OP_NOT, abi.BOOLEAN, a)
 def if_(c, a, b): return special(abi.FORM_IF, a.type, c, a, b)
 def coalesce(*args): return special(abi.FORM_COALESCE, args[0].type, *args)
+
+
+def substr(x, start, length=None):
+    """substr(x, start[, length]): code points, 1-based (StringFunctions.substring)"""
+    args = [x, _lift(start, abi.BIGINT)] + ([] if length is None else [_lift(length, abi.BIGINT)])
+    return call(abi.OP_SUBSTR, abi.VARCHAR, *args)
+
+
+def length(x): return call(abi.OP_LENGTH, abi.BIGINT, x)
+def year(d): return call(abi.OP_YEAR, abi.BIGINT, d)
+def month(d): return call(abi.OP_MONTH, abi.BIGINT, d)
+def day(d): return call(abi.OP_DAY, abi.BIGINT, d)
 
 
 def serialize(expr):
