@@ -1576,6 +1576,10 @@ static void min_max_update(acc_state* s, int is_min, const orc_val* v)
             c = m > 0 ? memcmp(v->s, s->str, (size_t)m) : 0;
             if (c == 0) c = v->slen < s->slen ? -1 : (v->slen > s->slen ? 1 : 0);
         }
+        else if (v->type == PA_LONG_DECIMAL) { /* LongDecimalType's comparison: the signed 128-bit values */
+            const __int128 held = s->dneg ? -(__int128)s->dmag : (__int128)s->dmag;
+            c = v->q < held ? -1 : (v->q > held ? 1 : 0);
+        }
         else {
             c = type_is_fp(v->type) ? double_compare(v->d, s->dsum) : (v->i < s->lsum ? -1 : (v->i > s->lsum ? 1 : 0));
         }
@@ -1585,6 +1589,10 @@ static void min_max_update(acc_state* s, int is_min, const orc_val* v)
         s->has_value = 1;
         s->dsum = v->d;
         s->lsum = v->i;
+        if (v->type == PA_LONG_DECIMAL) {
+            s->dneg = v->q < 0;
+            s->dmag = v->q < 0 ? (u128)(-v->q) : (u128)v->q;
+        }
         if (v->type == PA_VARCHAR) {
             free(s->str);
             s->str = (uint8_t*)malloc((size_t)(v->slen > 0 ? v->slen : 1));
@@ -1905,7 +1913,10 @@ int32_t orc_hash_agg_build_result(orc_hash_agg* a, pa_page* out)
                             a->error = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
                         }
                     }
-                    else { v.d = st[g].dsum; v.i = st[g].lsum; v.q = st[g].lsum; v.s = st[g].str; v.slen = st[g].slen; }
+                    else {
+                        v.d = st[g].dsum; v.i = st[g].lsum; v.s = st[g].str; v.slen = st[g].slen;
+                        v.q = b.type == PA_LONG_DECIMAL ? (st[g].dneg ? -(__int128)st[g].dmag : (__int128)st[g].dmag) : (__int128)st[g].lsum;
+                    }
                     cb_append(&b, &v);
                 }
                 cb_finish(&b, &out->columns[c++]);
@@ -1939,7 +1950,11 @@ int32_t orc_hash_agg_build_result(orc_hash_agg* a, pa_page* out)
                         if (s->overflow != 0 || ld_overflows(v.q)) a->error = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
                     }
                     else if (type_is_fp(out_type)) v.d = out_type == PA_REAL ? (double)(float)s->dsum : s->dsum; /* RealSumAggregation.output: (float) sum */
-                    else v.i = s->lsum;
+                    else {
+                        /* a 32-bit result column (sum over INTEGER: the reference only has sum(BIGINT)) holds the total or fails */
+                        if (type_width(out_type) == 4 && (s->lsum > INT32_MAX || s->lsum < INT32_MIN)) a->error = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;
+                        v.i = s->lsum;
+                    }
                     break;
                 case PA_AGG_AVG:
                     if (s->count == 0) v.is_null = 1;
@@ -1955,7 +1970,10 @@ int32_t orc_hash_agg_build_result(orc_hash_agg* a, pa_page* out)
                     break;
                 default:
                     if (!s->has_value) v.is_null = 1;
-                    else { v.d = s->dsum; v.i = s->lsum; v.q = s->lsum; v.s = s->str; v.slen = s->slen; }
+                    else {
+                        v.d = s->dsum; v.i = s->lsum; v.s = s->str; v.slen = s->slen;
+                        v.q = out_type == PA_LONG_DECIMAL ? (s->dneg ? -(__int128)s->dmag : (__int128)s->dmag) : (__int128)s->lsum;
+                    }
                     break;
             }
             cb_append(&b, &v);
@@ -1963,7 +1981,7 @@ int32_t orc_hash_agg_build_result(orc_hash_agg* a, pa_page* out)
         cb_finish(&b, &out->columns[c++]);
     }
     if (a->error) {
-        return fail(a->error, "Decimal overflow");
+        return fail(a->error, "Decimal overflow (or an INTEGER sum beyond 32 bits)");
     }
     return 1;
 }

@@ -418,13 +418,13 @@ void FusedGen::row_function(const std::string& name)
     src << body.str();
     // values needed after the selected-only block are declared up front
     for (int w = 0; w < k.nw; w++) {
-        src << "bool u" << w << " = false; " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w << " = 0;\n";
+        src << "bool " << uflag(w) << " = false; " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w << " = 0;\n";
     }
     const bool key32 = variant == V_LDS && k.packed_key;  // (the few-groups tier's 32-bit key table: fused_tier_lds.cpp)
     if (key32) src << "u32 key = 0u;\n";
     else if (k.w > 0) src << "u64 key[PA_KW];\n#pragma unroll\nfor (int i = 0; i < PA_KW; i++) key[i] = 0;\n";
     src << "if (sel) {\n" << build_loads.str() << inner.str();
-    for (int w = 0; w < k.nw; w++) src << "u" << w << " = " << words[w].cond << "; x" << w << " = " << words[w].val << ";\n";
+    for (int w = 0; w < k.nw; w++) src << uflag(w) << " = " << words[w].cond << "; x" << w << " = " << words[w].val << ";\n";
     if (brow) {
         src << "key[0] = (u64)(u32)jb;\n";
     }

@@ -89,6 +89,9 @@ struct FusedGen {
     int word(int kind, const std::string& cond, const std::string& val, const std::string& key);
     std::string minmax_image(const GenValue& x, bool is_min);
     std::string wtype(int w) const;   // C type of accumulator word w
+    // "does this row update word w": u<w> -- but u32, u64 and u128 are types the code behind the flags names, and a flag of that name
+    // would hide them (33 words are reached by the FINAL step over two short DECIMAL types)
+    static std::string uflag(int w) { return (w == 32 || w == 64 || w == 128 ? "u_" : "u") + std::to_string(w); }
     void row_filter();
     void group_keys();
     void accumulator_words();

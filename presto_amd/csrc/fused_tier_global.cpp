@@ -21,10 +21,10 @@ void FusedGen::global_accumulate_row()
 {
     src << "if (sel) {\n";
     for (int w = 0; w < k.nw; w++) {
-        if (words[w].kind == W_SUMF) src << "if (u" << w << ") acc.w" << w << " = acc.w" << w << " + x" << w << ";\n";
-        else if (words[w].kind == W_SUMI) src << "if (u" << w << ") acc.w" << w << " = pa_add_exact(acc.w" << w << ", x" << w << ", a.err);\n";
-        else if (words[w].kind == W_MAXU) src << "if (u" << w << ") acc.w" << w << " = x" << w << " > acc.w" << w << " ? x" << w << " : acc.w" << w << ";\n";
-        else src << "if (u" << w << ") acc.w" << w << " += x" << w << ";\n";
+        if (words[w].kind == W_SUMF) src << "if (" << uflag(w) << ") acc.w" << w << " = acc.w" << w << " + x" << w << ";\n";
+        else if (words[w].kind == W_SUMI) src << "if (" << uflag(w) << ") acc.w" << w << " = pa_add_exact(acc.w" << w << ", x" << w << ", a.err);\n";
+        else if (words[w].kind == W_MAXU) src << "if (" << uflag(w) << ") acc.w" << w << " = x" << w << " > acc.w" << w << " ? x" << w << " : acc.w" << w << ";\n";
+        else src << "if (" << uflag(w) << ") acc.w" << w << " += x" << w << ";\n";
     }
     src << "}\n";
 }

@@ -23,7 +23,7 @@ void FusedGen::table_accumulate()
     // accumulation of one row into the workgroup's LDS table / the HBM table
     src << "__device__ __forceinline__ void " << (gt_like ? "pa_acc_now" : "pa_acc")
         << "(const PaFusedArgs& a, PaAcc& acc, const bool sel, const i32 row, " << (gt_like ? "const i32 nrows, " : "") << "const u64 (&key)[PA_KW]";
-    for (int w = 0; w < k.nw; w++) src << ", const bool u" << w << ", const " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w;
+    for (int w = 0; w < k.nw; w++) src << ", const bool " << uflag(w) << ", const " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w;
     src << ")\n{\n";
     src << "if (sel) {\n  const u32 h = pa_key_hash(key, PA_KW);\n";
     if (lds_table) lds_table_accumulate_begin();
@@ -31,10 +31,10 @@ void FusedGen::table_accumulate()
     src << "  if (g >= 0) {\n    const u64 cap = (u64)a.gt_mask + 1ULL;\n";
     for (int w = 0; w < k.nw; w++) {
         std::string idx = std::to_string(w) + "ULL * cap + (u64)g";
-        if (words[w].kind == W_SUMF) src << "    if (u" << w << ") pa_gt_add_f64(acc.tv.words, " << idx << ", x" << w << ");\n";
-        else if (words[w].kind == W_SUMI) src << "    if (u" << w << ") pa_gt_add_i64_exact(acc.tv.words, " << idx << ", x" << w << ", a.err);\n";
-        else if (words[w].kind == W_MAXU) src << "    if (u" << w << ") pa_gt_max_u64(acc.tv.words, " << idx << ", x" << w << ");\n";
-        else src << "    if (u" << w << ") pa_gt_add_u64(acc.tv.words, " << idx << ", (u64)x" << w << ");\n";
+        if (words[w].kind == W_SUMF) src << "    if (" << uflag(w) << ") pa_gt_add_f64(acc.tv.words, " << idx << ", x" << w << ");\n";
+        else if (words[w].kind == W_SUMI) src << "    if (" << uflag(w) << ") pa_gt_add_i64_exact(acc.tv.words, " << idx << ", x" << w << ", a.err);\n";
+        else if (words[w].kind == W_MAXU) src << "    if (" << uflag(w) << ") pa_gt_max_u64(acc.tv.words, " << idx << ", x" << w << ");\n";
+        else src << "    if (" << uflag(w) << ") pa_gt_add_u64(acc.tv.words, " << idx << ", (u64)x" << w << ");\n";
     }
     // no room for this row's group: spill the row; the host rehashes and replays the spilled rows
     if (variant == V_GT) {
@@ -59,11 +59,11 @@ void FusedGen::gt_run_combining()
     for (int w = 0; w < k.nw; w++) src << ", acc.pu" << w << ", acc.px" << w;
     src << ");\n  if (doit) acc.pn = 0;\n}\n";
     src << "__device__ __forceinline__ void pa_acc(const PaFusedArgs& a, PaAcc& acc, const bool sel, const i32 row, const u64 (&key)[PA_KW]";
-    for (int w = 0; w < k.nw; w++) src << ", const bool u" << w << ", const " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w;
+    for (int w = 0; w < k.nw; w++) src << ", const bool " << uflag(w) << ", const " << (words[w].kind == W_SUMF ? "double" : (words[w].kind == W_MAXU ? "u64" : "i64")) << " x" << w;
     src << ")\n{\n  bool same = sel && acc.pn > 0;\n#pragma unroll\n  for (int w = 0; w < PA_KW; w++) same = same && key[w] == acc.pk[w];\n"
            "  pa_flush(a, acc, !same);\n  if (sel) {\n    if (acc.pn == 0) {\n#pragma unroll\n      for (int w = 0; w < PA_KW; w++) acc.pk[w] = key[w];\n"
            "      acc.prow = row;\n      acc.pn = 1;\n";
-    for (int w = 0; w < k.nw; w++) src << "      acc.pu" << w << " = u" << w << "; acc.px" << w << " = x" << w << ";\n";
+    for (int w = 0; w < k.nw; w++) src << "      acc.pu" << w << " = " << uflag(w) << "; acc.px" << w << " = x" << w << ";\n";
     src << "    } else {\n      acc.pn = row - acc.prow + 1;\n";
     for (int w = 0; w < k.nw; w++) {
         const std::string P = "acc.px" + std::to_string(w), U = "acc.pu" + std::to_string(w), X = "x" + std::to_string(w);
@@ -71,7 +71,7 @@ void FusedGen::gt_run_combining()
         if (words[w].kind == W_SUMF || words[w].kind == W_CNT) comb = P + " + " + X;
         else if (words[w].kind == W_SUMI) comb = "pa_add_exact(" + P + ", " + X + ", a.err)";
         else comb = "(" + X + " > " + P + " ? " + X + " : " + P + ")";
-        src << "      if (u" << w << ") { " << P << " = " << U << " ? " << comb << " : " << X << "; " << U << " = true; }\n";
+        src << "      if (" << uflag(w) << ") { " << P << " = " << U << " ? " << comb << " : " << X << "; " << U << " = true; }\n";
     }
     src << "    }\n  }\n}\n\n";
 }
@@ -79,7 +79,7 @@ void FusedGen::gt_run_combining()
 void FusedGen::table_accumulate_row()
 {
     src << "pa_acc(a, acc, sel, row, key";
-    for (int w = 0; w < k.nw; w++) src << ", u" << w << ", x" << w;
+    for (int w = 0; w < k.nw; w++) src << ", " << uflag(w) << ", x" << w;
     src << ");\n";
 }
 

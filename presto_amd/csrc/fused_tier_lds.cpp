@@ -70,16 +70,16 @@ void FusedGen::lds_accumulate_row()
     for (int w = 0; w < k.nw; w++) {
         std::string idx = "pa_accw[(" + std::to_string(w) + " * PA_C + g) * 64 + acc.lane]";
         if (words[w].kind == W_SUMF) {
-            src << "    if (u" << w << ") __hip_atomic_fetch_add((double*)&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
+            src << "    if (" << uflag(w) << ") __hip_atomic_fetch_add((double*)&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
         }
         else if (words[w].kind == W_SUMI) {
-            src << "    if (u" << w << ") { i64* p = (i64*)&" << idx << "; *p = pa_add_exact(*p, x" << w << ", a.err); }\n";
+            src << "    if (" << uflag(w) << ") { i64* p = (i64*)&" << idx << "; *p = pa_add_exact(*p, x" << w << ", a.err); }\n";
         }
         else if (words[w].kind == W_MAXU) {
-            src << "    if (u" << w << ") { u64* p = &" << idx << "; if (x" << w << " > *p) *p = x" << w << "; }\n";
+            src << "    if (" << uflag(w) << ") { u64* p = &" << idx << "; if (x" << w << " > *p) *p = x" << w << "; }\n";
         }
         else {
-            src << "    if (u" << w << ") __hip_atomic_fetch_add(&" << idx << ", " << (words[w].val == "1" ? std::string("1ULL") : "(u64)x" + std::to_string(w))
+            src << "    if (" << uflag(w) << ") __hip_atomic_fetch_add(&" << idx << ", " << (words[w].val == "1" ? std::string("1ULL") : "(u64)x" + std::to_string(w))
                 << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
         }
     }

@@ -77,18 +77,18 @@ void FusedGen::lds_table_accumulate_begin()
     for (int w = 0; w < k.nw; w++) {
         std::string idx = "pa_lt_acc[ls * PA_NW + " + std::to_string(w) + "]";
         if (words[w].kind == W_SUMF) {
-            src << "    if (u" << w << ") __hip_atomic_fetch_add((double*)&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
+            src << "    if (" << uflag(w) << ") __hip_atomic_fetch_add((double*)&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
         }
         else if (words[w].kind == W_SUMI) {
-            src << "    if (u" << w << ") { i64 o = (i64)__hip_atomic_fetch_add(&" << idx << ", (u64)x" << w
+            src << "    if (" << uflag(w) << ") { i64 o = (i64)__hip_atomic_fetch_add(&" << idx << ", (u64)x" << w
                 << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); i64 r; if (__builtin_add_overflow(o, x" << w
                 << ", &r)) pa_raise(a.err, PA_DEV_ERR_OUT_OF_RANGE); }\n";
         }
         else if (words[w].kind == W_MAXU) {
-            src << "    if (u" << w << ") __hip_atomic_fetch_max(&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
+            src << "    if (" << uflag(w) << ") __hip_atomic_fetch_max(&" << idx << ", x" << w << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
         }
         else {
-            src << "    if (u" << w << ") __hip_atomic_fetch_add(&" << idx << ", " << ("(u64)x" + std::to_string(w))
+            src << "    if (" << uflag(w) << ") __hip_atomic_fetch_add(&" << idx << ", " << ("(u64)x" + std::to_string(w))
                 << ", __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);\n";
         }
     }

@@ -173,9 +173,9 @@ void FusedGen::brow_declarations()
            "__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, \"wavefront\"); } while (0)\n";
     // noting row `slot` of the quad (a literal at every call site: the arrays stay in registers)
     src << "__device__ __forceinline__ void pa_acc(const PaFusedArgs& a, PaAcc& acc, const int slot, const bool sel, const u64 (&key)[PA_KW]";
-    for (int w = 0; w < k.nw; w++) src << ", const bool u" << w << ", const " << wtype(w) << " x" << w;
+    for (int w = 0; w < k.nw; w++) src << ", const bool " << uflag(w) << ", const " << wtype(w) << " x" << w;
     src << ")\n{\n  acc.ev[slot] = sel;\n  acc.eg[slot] = (u32)key[0];\n";
-    for (int w = 0; w < k.nw; w++) src << "  acc.eu" << w << "[slot] = u" << w << "; acc.ex" << w << "[slot] = x" << w << ";\n";
+    for (int w = 0; w < k.nw; w++) src << "  acc.eu" << w << "[slot] = " << uflag(w) << "; acc.ex" << w << "[slot] = x" << w << ";\n";
     src << "  if (slot > 0 && sel && acc.ev[slot > 0 ? slot - 1 : 0] && acc.eg[slot > 0 ? slot - 1 : 0] == acc.eg[slot]) {\n    const int p = slot > 0 ? slot - 1 : 0;\n";
     for (int w = 0; w < k.nw; w++) {
         const std::string P = "acc.ex" + std::to_string(w) + "[p]", X = "acc.ex" + std::to_string(w) + "[slot]";
@@ -255,7 +255,7 @@ void FusedGen::brow_declarations()
 void FusedGen::brow_accumulate_row()
 {
     src << "pa_acc(a, acc, slot, sel, key";
-    for (int w = 0; w < k.nw; w++) src << ", u" << w << ", x" << w;
+    for (int w = 0; w < k.nw; w++) src << ", " << uflag(w) << ", x" << w;
     src << ");\n";
 }
 

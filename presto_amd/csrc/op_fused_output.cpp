@@ -111,6 +111,8 @@ bool FusedAggregationOperator::emit_on_device(const KernelInfo& ki, int64_t grou
         const int type = real_out ? PA_REAL : (as_double ? PA_DOUBLE : ((ag.fn == PA_AGG_SUM) ? spec_.proj[value_proj].root_type() : PA_BIGINT));
         const int kind = ag.fn == PA_AGG_SUM ? GT_EMIT_SUM : (ag.fn == PA_AGG_AVG ? GT_EMIT_AVG : GT_EMIT_COUNT);
         if (ag.fn != PA_AGG_SUM && ag.fn != PA_AGG_AVG && ag.fn != PA_AGG_COUNT && ag.fn != PA_AGG_COUNT_STAR) return false;
+        // an integer sum in a 32-bit column is range-checked where the column is written: on the host (build_output)
+        if (kind == GT_EMIT_SUM && !as_double && type_width(type) == 4) return false;
         GtEmitCol* c = add(kind, type);
         if (!c) return false;
         c->cw = cw;
@@ -656,7 +658,10 @@ void FusedAggregationOperator::assemble_output(const KernelInfo& ki, const std::
                 memcpy(&data[(size_t)g * 4], &f, 4);
             }
             else {
-                int32_t v = (int32_t)(int64_t)bits;
+                // sum(INTEGER) keeps its INTEGER column: a total beyond it is an error, never a narrowed value
+                const int64_t total = (int64_t)bits;
+                PA_REQUIRE(total >= INT32_MIN && total <= INT32_MAX, PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, "integer sum out of range");
+                int32_t v = (int32_t)total;
                 memcpy(&data[(size_t)g * 4], &v, 4);
             }
         }

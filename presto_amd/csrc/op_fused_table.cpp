@@ -192,12 +192,13 @@ void FusedAggregationOperator::run_page_partitioned(const std::string& sig, cons
     int moved = 0;
     for (int c = 0; c < spec_.n_in && ldsp; c++) {
         if (!spec_.used_channel[c]) continue;
-        ldsp = !dp.cols[c].varwidth;
+        // (the multisplit moves 1-, 4- and 8-byte elements: a LONG_DECIMAL input keeps the position list, as a VARCHAR one does)
+        ldsp = !dp.cols[c].varwidth && type_width(dp.cols[c].type) <= 8;
         moved += 1 + (dp.cols[c].nulls ? 1 : 0);
     }
     ldsp = ldsp && moved <= kMsplitMaxCols && !getenv("PRESTO_AMD_NO_MSPLIT");
     if (!ldsp && ldsp_.parts == 0) ldsp_.want = false;
-    if (!ldsp) partitions = std::min(partitions, 2048);
+    if (!ldsp) partitions = std::min(partitions, 512);  // (the position list is made for at most 512 partitions + 1 for the filtered rows)
     const Compiled& lk = kernel_for(sig, layout, ldsp ? V_LDSP : V_LDSH);
     cur_sig_ = &sig;
     cur_layout_ = &layout;
@@ -246,7 +247,7 @@ void FusedAggregationOperator::run_page_partitioned(const std::string& sig, cons
         // ways) and the LDS-table kernel reads its slice contiguously; with a position list it pays a cache line per row
         // and column.  VARCHAR inputs keep the position list.
         bool reorder = !getenv("PRESTO_AMD_NO_MSPLIT");
-        for (int c = 0; c < spec_.n_in && reorder; c++) reorder = !spec_.used_channel[c] || !dp.cols[c].varwidth;
+        for (int c = 0; c < spec_.n_in && reorder; c++) reorder = !spec_.used_channel[c] || (!dp.cols[c].varwidth && type_width(dp.cols[c].type) <= 8);
         if (reorder) {
             std::vector<MsplitCol> mc;
             DevPage rp;

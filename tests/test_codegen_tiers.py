@@ -139,3 +139,26 @@ def test_probe_stage_tiers_generate_and_compile():
             for v in variants:
                 rc = L.pa_codegen_compile_fused_join(C.byref(d), C.byref(build), v)
                 assert rc > 1000, (group_by, TIER_NAMES[v], L.pa_last_error())
+
+
+def test_final_step_of_more_than_32_accumulator_words_compiles():
+    """the FINAL step keeps a count word and the value words per aggregate: all six aggregates over two short DECIMAL types are 36 words,
+    and the generated per-word names must not collide with the type names of the generated source (u32)"""
+    from presto_amd.exchange import partial_layout
+    L = lib()
+    L.pa_codegen_fused_layout.restype = C.c_int64
+    L.pa_codegen_fused_layout.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_char_p, C.c_int64]
+    aggs = []
+    for ch, t in ((1, abi.decimal(8, 2)), (2, abi.decimal(12, 2))):
+        aggs += [(abi.AGG_COUNT_STAR, -1, None), (abi.AGG_COUNT, ch, t), (abi.AGG_SUM, ch, t), (abi.AGG_AVG, ch, t), (abi.AGG_MIN, ch, t), (abi.AGG_MAX, ch, t)]
+    for keys, variants in (([abi.BIGINT], (V_GT, V_LDSH)), ([], (V_GLOBAL,))):
+        ptypes, faggs = partial_layout(keys, aggs)
+        d, keep = fused_aggregation_desc(ptypes, None, [field(i, t) for i, t in enumerate(ptypes)], [0] if keys else [], faggs, step=abi.STEP_FINAL)
+        for v in variants:
+            need = L.pa_codegen_fused_layout(C.byref(d), v, 0, 0, None, 0)
+            assert need > 0, L.pa_last_error()
+            buf = C.create_string_buffer(need)
+            L.pa_codegen_fused_layout(C.byref(d), v, 0, 0, buf, need)
+            assert "u_32" in buf.value.decode(), TIER_NAMES[v]            # 33 words or more
+            rc = L.pa_codegen_fused_layout(C.byref(d), v, 0, 1, None, 0)
+            assert rc > 1000, (TIER_NAMES[v], rc, L.pa_last_error().decode()[-600:])
