@@ -195,6 +195,11 @@ KernelInfo generate(const Spec& s, const std::vector<ChannelLayout>& layout, int
 // it, instead of loading the next quad first.  The switch changes the generated source, hence the kernel's name; an operator's plan
 // fingerprint carries it, so that kernels generated under another setting are not shared.
 int lds_pipe_level();
+// PRESTO_AMD_NT (default 1): the cache policy of the 16-byte column loads of the ungrouped tier's staged page loop.  0 = default-policy
+// loads (the source of before the switch, byte for byte), 1 = non-temporal loads for stage 0 (the columns every row reads: each byte
+// is read once per pass), 2 = also for the masked loads of the later stages, whose dead quads re-read the column's first line
+// (measured slower on Q6: DESIGN section 4).  Part of the plan fingerprint, as PRESTO_AMD_LDS_PIPE is.
+int nt_level();
 
 }  // namespace fused
 }  // namespace pa

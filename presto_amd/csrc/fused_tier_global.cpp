@@ -5,6 +5,8 @@
 #include "fused_codegen.hpp"
 #include "scan_kernels.hpp"
 
+#include <algorithm>
+#include <cstdlib>
 #include <set>
 
 namespace pa {
@@ -75,6 +77,12 @@ void FusedGen::global_kernel_end()
             << "; i++) r += pa_scnt[i * " << ns << " + threadIdx.x];\n"
                "        a.slab[(u64)gridDim.x * PA_NW + (u64)blockIdx.x * " << ns << " + threadIdx.x] = r;\n    }\n";
     }
+}
+
+int nt_level()
+{
+    const char* e = getenv("PRESTO_AMD_NT");
+    return e ? std::max(0, std::min(2, atoi(e))) : 1;
 }
 
 // ---- V_GLOBAL_S: the staged page loop ----
@@ -179,13 +187,20 @@ void FusedGen::staged_page_loop()
         return a;
     };
     // the load of variable v for the quad of holder h, `q` (the rows alive: holder h's flags); rows = the rows of the quad the
-    // variable carries
+    // variable carries.  The 16-byte loads of column values are non-temporal under PRESTO_AMD_NT: from level 1 those of stage 0, which
+    // every row asks for, from level 2 also the later stages', whose dead quads re-read one line (both halves of a quad alike)
+    const int nt = nt_level();
+    auto streamed = [&](const VectorVar& v) {
+        return (v.name[0] == 'A' || v.name[0] == 'B') && v.type != "u32" && nt >= (stage_of(v) == 0 ? 1 : 2);
+    };
     auto masked_load = [&](const VectorVar& v, int h, const std::string& q) {
         std::string any;
         const int r0 = v.per_quad == 2 ? 2 * v.half : 0, r1 = v.per_quad == 2 ? r0 + 2 : 4;
         for (int r = r0; r < r1; r++) any += (any.empty() ? "" : " || ") + std::string("!") + H(h) + "d" + std::to_string(r);
         const std::string idx = v.per_quad == 2 ? "2 * " + q + (v.half ? " + 1" : "") : (v.per_quad == 0 ? "4 * " + q + " + 4" : q);
-        const std::string ld = "((const " + v.type + "*)" + v.array + ")[(" + any + ") ? " + idx + " : " + (v.per_quad == 0 ? "4" : "0") + "]";
+        std::string ld = "((const " + v.type + "*)" + v.array + ")[(" + any + ") ? " + idx + " : " + (v.per_quad == 0 ? "4" : "0") + "]";
+        // (the element's address is named first, so that the load itself still reads `((const T*)a.v[c])[index];`)
+        if (streamed(v)) ld = "({ const " + v.type + "* const pa_p = &" + ld + "; __builtin_nontemporal_load(pa_p); })";
         return v.maybe_null ? "(" + v.array + " ? " + ld + " : 0u)" : ld;
     };
     for (int k = 1; k < S; k++) src << "    u32 pa_cnt" << k << " = 0u;\n";
