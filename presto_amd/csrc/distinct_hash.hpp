@@ -1,5 +1,5 @@
 // distinct_hash.hpp -- what the operators over GroupByHash.getGroupIds share (op_distinct.cpp, op_row_number.cpp): the growing key table
-// of distinct_kernels.hpp with its key store and string interners, and Block.copyPositions of one channel.
+// of distinct_kernels.hpp with its key store and string interners.
 #pragma once
 
 #include <algorithm>
@@ -202,40 +202,6 @@ private:
     uint32_t capacity_ = 0, store_capacity_ = 0, seq_ = 0;
     int64_t count_ = 0, fed_rows_ = 0;
     std::deque<std::pair<uint32_t, int32_t>> fed_;   // pages whose counter has not landed yet: {sequence number, rows}
-};
-
-// The rows at `positions` of a staged column as a flat copy (DistinctLimit's new keys, RowNumber's rows under the cap)
-class PositionGather {
-public:
-    // Block.copyPositions of one channel
-    void copy_positions(const DevColumn& src, const int32_t* positions, int32_t k, OutColumn& o, hipStream_t s)
-    {
-        o.type = src.type;
-        o.varwidth = src.varwidth;
-        o.has_nulls = src.nulls != nullptr;
-        o.is_view = false;
-        o.host_ready = false;
-        if (src.nulls) launch_gather_nulls(src.nulls, positions, k, static_cast<uint8_t*>(o.nulls.ensure((size_t)k)), s);
-        if (!src.varwidth) {
-            const int w = type_width(src.type);
-            launch_gather_flat(src.values, w, positions, k, o.values.ensure((size_t)k * w), s);
-            return;
-        }
-        // VARCHAR: lengths -> exclusive scan -> byte copy
-        int32_t* offs = static_cast<int32_t*>(o.offsets.ensure((size_t)(k + 1) * 4));
-        int32_t* total = static_cast<int32_t*>(total_.ensure(64));
-        launch_varwidth_lengths(positions, k, src.offsets, src.nulls, offs, s);
-        launch_exclusive_scan_i32(offs, offs, k, total, scan_temp_.ensure(scan_temp_bytes(k)), s);
-        int32_t h_total = 0;
-        read_back(&h_total, total, 4, s);
-        uint8_t* bytes = static_cast<uint8_t*>(o.values.ensure((size_t)(h_total > 0 ? h_total : 1)));
-        launch_varwidth_copy(positions, k, src.offsets, static_cast<const uint8_t*>(src.values), src.nulls, offs, bytes, total, s);
-    }
-
-    size_t bytes() const { return scan_temp_.capacity() + total_.capacity(); }
-
-private:
-    DevBuf scan_temp_, total_;
 };
 
 }  // namespace pa

@@ -5,8 +5,8 @@
 //   append_page / append_positions    PagesIndex.addPage: a staged page (or its rows at `positions`) behind the rows held
 //   keep_positions                    the rows at `rowids` into fresh columns (a prune)
 //   gather_sorted                     PagesIndex.appendTo: channels through a permutation into output columns
-// Host cost per VARCHAR channel and call: one read-back (two 4-byte copies, one stream sync; gather_sorted: one 4-byte copy, one sync);
-// a fixed-width channel costs none.  Nothing here waits at the end of a call: the callers keep their own.  The row-count limit of a
+// Host cost per VARCHAR channel and call: one read-back of 4 bytes (append_page: two 4-byte copies), one stream sync; a fixed-width
+// channel costs none.  The gathers by position are PositionGather's (position_gather.hpp).  Nothing here waits at the end of a call: the callers keep their own.  The row-count limit of a
 // sort stays with the operators (they word it differently, and TopNRanking prunes before it gives up).
 #pragma once
 
@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "device_page.hpp"
-#include "distinct_hash.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 #include "static_kernels.hpp"
 
@@ -71,9 +71,7 @@ struct HeldRows {
             const DevColumn& src = in.cols[c];
             OutColumn& h = cols[c];
             if (h.varwidth) {
-                gather.copy_positions(src, positions, k, varchar_tmp, s);   // offsets from 0, k + 1 of them
-                int32_t add = 0;
-                read_back(&add, varchar_tmp.offsets.as<int32_t>() + k, 4, s);
+                const int32_t add = gather.copy_positions(src, positions, k, varchar_tmp, s);   // offsets from 0, k + 1 of them
                 char* v = append_offsets(c, varchar_tmp.offsets.as<int32_t>(), k, add, s);
                 if (add) PA_HIP(hipMemcpyAsync(v, varchar_tmp.values.ptr(), (size_t)add, hipMemcpyDeviceToDevice, s));
             }
@@ -93,12 +91,7 @@ struct HeldRows {
         for (size_t c = 0; c < cols.size(); c++) {
             if (!held[c]) continue;
             OutColumn fresh;
-            gather.copy_positions(view((int32_t)c), rowids, kept, fresh, s);
-            if (fresh.varwidth) {
-                int32_t bytes = 0;
-                read_back(&bytes, fresh.offsets.as<int32_t>() + kept, 4, s);
-                var_bytes[c] = bytes;
-            }
+            var_bytes[c] = gather.copy_positions(view((int32_t)c), rowids, kept, fresh, s);
             cols[c] = std::move(fresh);   // (the old arrays go back to the pool tagged with this stream)
         }
         rows = kept;
@@ -119,10 +112,9 @@ struct HeldRows {
     // out_cols[j] = channels[j] of the n rows in the order of perm.  skip (may be null): (*skip)[j] marks a column the caller has
     // produced already, which has no NULLs.  The fixed-width channels and every NULL flag array go through the permutation by ONE
     // launch per GATHER_MULTI_MAX_COLS columns: the permutation is read once, the random reads of all channels are in flight together.
-    // A VARCHAR channel: lengths -> scan -> copy, the byte total read back.  scan_temp (grown here when a VARCHAR channel needs it)
-    // and total_word (4 bytes of device memory) are the caller's, and counted by it.
+    // A VARCHAR channel's values go through gather.copy_varwidth (its scratch is the caller's, and counted by it).
     void gather_sorted(const int32_t* perm, int64_t n, const std::vector<int32_t>& channels, const std::vector<bool>* skip,
-                       std::vector<OutColumn>& out_cols, DevBuf& scan_temp, int32_t* total_word, hipStream_t s) const
+                       std::vector<OutColumn>& out_cols, PositionGather& gather, hipStream_t s) const
     {
         GatherMultiArgs gm;
         memset(&gm, 0, sizeof gm);
@@ -143,15 +135,7 @@ struct HeldRows {
             GatherMultiCol& gc = gm.col[gm.ncols];
             memset(&gc, 0, sizeof gc);
             gc.width = 1;
-            if (h.varwidth) {
-                int32_t* lens = static_cast<int32_t*>(oc.offsets.ensure((size_t)(n + 1) * 4));
-                launch_varwidth_lengths(perm, n, h.offsets, h.nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, n, total_word, scan_temp.ensure(scan_temp_bytes(n)), s);
-                int32_t h_total = 0;
-                read_back(&h_total, total_word, 4, s);
-                launch_varwidth_copy(perm, n, h.offsets, static_cast<const uint8_t*>(h.values), h.nulls, lens,
-                                     static_cast<uint8_t*>(oc.values.ensure((size_t)(h_total > 0 ? h_total : 1))), total_word, s);
-            }
+            if (h.varwidth) gather.copy_varwidth(h, perm, (int32_t)n, oc.offsets, oc.values, s);
             else {
                 const int w = type_width(h.type);   // (1, 4, 8, or 16 for a LONG_DECIMAL: creation refused every other type)
                 gc.src = h.values;

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "device_page.hpp"
 #include "join_kernels.hpp"
 
 namespace pa {
@@ -22,6 +23,16 @@ struct BuildColumn {
     DevBuf values, offsets, nulls;
     bool has_nulls = false;
     int64_t bytes = 0;  // VARWIDTH: bytes used
+    DevColumn view() const
+    {
+        DevColumn c;
+        c.type = type;
+        c.varwidth = varwidth;
+        c.values = values.ptr();
+        c.offsets = offsets.as<int32_t>();
+        c.nulls = has_nulls ? nulls.as<uint8_t>() : nullptr;
+        return c;
+    }
 };
 
 // The lookup source shared between the build operator and its probe operators

@@ -15,6 +15,7 @@
 
 #include "distinct_hash.hpp"
 #include "operator.hpp"
+#include "position_gather.hpp"
 #include "row_number_kernels.hpp"
 
 // (internal to the library: the inline functions and classes here stay out of its exported symbols)

@@ -26,6 +26,7 @@
 #include "jit.hpp"
 #include "join_source.hpp"
 #include "operator.hpp"
+#include "position_gather.hpp"
 #include "rowgen.hpp"
 #include "scan_kernels.hpp"
 
@@ -642,24 +643,10 @@ public:
                 continue;
             }
             if (oc.varwidth) {
-                // Block.copyPositions for a VariableWidthBlock: lengths -> exclusive scan -> byte copy
-                const DevColumn& src = in_.cols[e.node(e.root).channel];
-                int32_t* lens = static_cast<int32_t*>(oc.offsets.ensure((size_t)(count + 1) * 4));
-                launch_varwidth_lengths(positions_.as<int32_t>(), count, src.offsets, src.nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, count, ctl_ + 2, scan_temp_.ensure(scan_temp_bytes(count)), s);
-                PA_HIP(hipMemcpyAsync(h_ctl_ + 2, ctl_ + 2, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                int32_t total = h_ctl_[2];
-                uint8_t* bytes = static_cast<uint8_t*>(oc.values.ensure((size_t)(total > 0 ? total : 1)));
-                launch_varwidth_copy(positions_.as<int32_t>(), count, src.offsets, static_cast<const uint8_t*>(src.values), src.nulls, lens, bytes,
-                                     ctl_ + 2, s);
-                if (src.nulls) {
-                    launch_gather_nulls(src.nulls, positions_.as<int32_t>(), count, static_cast<uint8_t*>(oc.nulls.ensure((size_t)count)), s);
-                    oc.has_nulls = true;
-                }
-                else {
-                    oc.has_nulls = false;
-                }
+                // Block.copyPositions for a VariableWidthBlock, out under the type the projection declares
+                gather_.copy_positions(in_.cols[e.node(e.root).channel], positions_.as<int32_t>(), count, oc, s);
+                oc.type = e.root_type();
+                oc.varwidth = true;
             }
         }
         *out_count = count;
@@ -944,6 +931,7 @@ private:
     DevPage in_;
     bool in_device_ = false, finishing_ = false, pending_ = false, need_positions_ = false;
     DevBuf ctl_buf_, sel4_, tile_counts_, positions_, scan_temp_;
+    PositionGather gather_;   // (the VARCHAR projections' copyPositions)
     PinnedBuf h_ctl_buf_;
     int32_t* ctl_ = nullptr;
     int32_t* h_ctl_ = nullptr;

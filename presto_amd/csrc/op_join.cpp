@@ -22,6 +22,7 @@
 #include "join_source.hpp"
 #include "keyed_operator.hpp"
 #include "operator.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 #include "static_kernels.hpp"
 
@@ -724,19 +725,16 @@ public:
             return true;
         };
         for (int c : output_channels_) {
-            const DevColumn& src = in_.cols[c];
-            const void* values = src.varwidth ? src.values : static_cast<const char*>(src.values) + (size_t)lo * type_width(src.type);
+            const DevColumn src = rows_from(in_.cols[c], lo);
             OutColumn& out_col = out_cols_[oc++];
-            if (!src.varwidth && flat(src.type, values, src.nulls ? src.nulls + lo : nullptr, 0, false, out_col)) continue;
-            gather_column(src.type, src.varwidth, values, src.offsets ? src.offsets + lo : nullptr, src.nulls ? src.nulls + lo : nullptr, probe_idx, total_out,
-                          out_col, s);
+            if (!src.varwidth && flat(src.type, src.values, src.nulls, 0, false, out_col)) continue;
+            gather_column(src, probe_idx, total_out, out_col, s);
         }
         for (int c : ls_->output_channels) {
-            const BuildColumn& src = ls_->cols[c];
+            const DevColumn src = ls_->cols[c].view();
             OutColumn& out_col = out_cols_[oc++];
-            if (!src.varwidth && flat(src.type, src.values.ptr(), src.has_nulls ? src.nulls.as<uint8_t>() : nullptr, 1, probe_outer_, out_col)) continue;
-            gather_column(src.type, src.varwidth, src.values.ptr(), src.offsets.as<int32_t>(), src.has_nulls ? src.nulls.as<uint8_t>() : nullptr,
-                          build_pos, total_out, out_col, s, probe_outer_);
+            if (!src.varwidth && flat(src.type, src.values, src.nulls, 1, probe_outer_, out_col)) continue;
+            gather_column(src, build_pos, total_out, out_col, s, probe_outer_);
         }
         launch_gather_multi(gm, s);
         publish_output(out_cols_, total_out, output_mem_, s, out, out_storage_);
@@ -909,15 +907,8 @@ public:
             cols[c].encoding = filter_types_[c] == PA_VARCHAR ? PA_VARWIDTH : PA_FLAT;
             if (!filter_used_[c] && (int)c != nb + n_probe_channels_) continue;
             OutColumn& oc = pair_cols_[c];
-            if ((int)c < nb) {
-                const BuildColumn& src = ls_->cols[c];
-                gather_column(src.type, src.varwidth, src.values.ptr(), src.offsets.as<int32_t>(), src.has_nulls ? src.nulls.as<uint8_t>() : nullptr, cand_build, total, oc, s);
-            }
-            else if ((int)c < nb + n_probe_channels_) {
-                const DevColumn& src = in_.cols[c - nb];
-                const void* values = src.varwidth ? src.values : static_cast<const char*>(src.values) + (size_t)lo * type_width(src.type);
-                gather_column(src.type, src.varwidth, values, src.offsets ? src.offsets + lo : nullptr, src.nulls ? src.nulls + lo : nullptr, cand_probe, total, oc, s);
-            }
+            if ((int)c < nb) gather_column(ls_->cols[c].view(), cand_build, total, oc, s);
+            else if ((int)c < nb + n_probe_channels_) gather_column(rows_from(in_.cols[c - nb], lo), cand_probe, total, oc, s);
             else {
                 oc.type = PA_INTEGER;
                 oc.varwidth = false;
@@ -987,40 +978,30 @@ public:
 
 private:
     // null_rows: positions may hold -1 = a NULL row (build side of a probe-outer join)
-    void gather_column(int32_t type, bool varwidth, const void* values, const int32_t* offsets, const uint8_t* nulls, const int32_t* positions,
-                       int32_t count, OutColumn& oc, hipStream_t s, bool null_rows = false)
+    void gather_column(const DevColumn& src, const int32_t* positions, int32_t count, OutColumn& oc, hipStream_t s, bool null_rows = false)
     {
-        oc.type = type;
-        oc.varwidth = varwidth;
+        oc.type = src.type;
+        oc.varwidth = src.varwidth;
         oc.is_view = false;
         oc.host_ready = false;
-        oc.has_nulls = nulls != nullptr || null_rows;
-        if (varwidth) {
-            int32_t* lens = static_cast<int32_t*>(oc.offsets.ensure((size_t)(count + 1) * 4));
-            launch_varwidth_lengths(positions, count, offsets, nulls, lens, s);
-            launch_sum_i32_i64(lens, count, reinterpret_cast<int64_t*>(ctl_ + 6), s);
-            launch_exclusive_scan_i32(lens, lens, count, ctl_ + 2, scan_temp_.ensure(scan_temp_bytes(count)), s);
-            PA_HIP(hipMemcpyAsync(h_ctl_ + 2, ctl_ + 2, 4, hipMemcpyDeviceToHost, s));
-            PA_HIP(hipMemcpyAsync(h_ctl_ + 6, ctl_ + 6, 8, hipMemcpyDeviceToHost, s));
-            PA_HIP(hipStreamSynchronize(s));
-            int64_t bytes64;
-            memcpy(&bytes64, h_ctl_ + 6, 8);
-            PA_REQUIRE(bytes64 < ((int64_t)1 << 31), PA_ERR_INSUFFICIENT_RESOURCES, "a join output page holds more than 2 GiB of VARCHAR bytes");
-            int32_t bytes = h_ctl_[2];
-            uint8_t* dst = static_cast<uint8_t*>(oc.values.ensure((size_t)(bytes > 0 ? bytes : 1)));
-            launch_varwidth_copy(positions, count, offsets, static_cast<const uint8_t*>(values), nulls, lens, dst, ctl_ + 2, s);
+        oc.has_nulls = src.nulls != nullptr || null_rows;
+        uint8_t* out_nulls = oc.has_nulls ? static_cast<uint8_t*>(oc.nulls.ensure((size_t)count)) : nullptr;
+        const int w = src.varwidth ? 0 : type_width(src.type);
+        if (src.varwidth) {
+            gather_.copy_varwidth(src, positions, count, oc.offsets, oc.values, s, "a join output page holds more than 2 GiB of VARCHAR bytes");
+            if (null_rows) launch_gather_or_null(nullptr, 0, src.nulls, positions, count, nullptr, out_nulls, s);
         }
-        else if (null_rows) {
-            int w = type_width(type);
-            launch_gather_or_null(values, w, nulls, positions, count, oc.values.ensure((size_t)count * w), static_cast<uint8_t*>(oc.nulls.ensure((size_t)count)), s);
-            return;
-        }
-        else {
-            int w = type_width(type);
-            launch_gather_flat(values, w, positions, count, oc.values.ensure((size_t)count * w), s);
-        }
-        if (null_rows) launch_gather_or_null(nullptr, 0, nulls, positions, count, nullptr, static_cast<uint8_t*>(oc.nulls.ensure((size_t)count)), s);
-        else if (nulls) launch_gather_nulls(nulls, positions, count, static_cast<uint8_t*>(oc.nulls.ensure((size_t)count)), s);
+        else if (null_rows) launch_gather_or_null(src.values, w, src.nulls, positions, count, oc.values.ensure((size_t)count * w), out_nulls, s);
+        else launch_gather_flat(src.values, w, positions, count, oc.values.ensure((size_t)count * w), s);
+        if (!null_rows && src.nulls) launch_gather_nulls(src.nulls, positions, count, out_nulls, s);
+    }
+    // the rows of a staged probe column from row `lo` on (a VARCHAR's bytes stay where the offsets point)
+    static DevColumn rows_from(DevColumn col, int32_t lo)
+    {
+        if (!col.varwidth) col.values = static_cast<const char*>(col.values) + (size_t)lo * type_width(col.type);
+        if (col.offsets) col.offsets += lo;
+        if (col.nulls) col.nulls += lo;
+        return col;
     }
 
     Stream stream_;
@@ -1035,6 +1016,7 @@ private:
     bool in_volatile_ = false;
     std::vector<DevBuf> kept_;  // keep_input: per channel values, offsets, NULL flags
     DevBuf ctl_buf_, hash_, head_, counts_, probe_idx_, build_pos_, scan_temp_, totals_;
+    PositionGather gather_;   // (the VARCHAR output channels' copyPositions)
     PinnedBuf h_totals_;
     bool totals_pending_ = false;
     bool eager_ = false;          // the page's pairs and output columns are already in the stream (emit_eagerly)
@@ -1080,8 +1062,6 @@ public:
             probe_output_types_.push_back(d->probe_types[c]);
         }
         output_mem_ = d->output_mem;
-        ctl_ = static_cast<int32_t*>(ctl_buf_.ensure(64));
-        h_ctl_ = static_cast<int32_t*>(h_ctl_buf_.ensure(64));
     }
     ~LookupOuterOperator() override { (void)hipStreamSynchronize(stream_.get()); }
     hipStream_t private_stream() override { return stream_.owned() ? stream_.get() : nullptr; }
@@ -1127,29 +1107,7 @@ public:
                 PA_HIP(hipMemsetAsync(o.values.ensure((size_t)count * type_width(t)), 0, (size_t)count * type_width(t), s));
             }
         }
-        for (int c : ls_->output_channels) {
-            const BuildColumn& src = ls_->cols[c];
-            OutColumn& o = out_cols_[oc++];
-            o.type = src.type;
-            o.varwidth = src.varwidth;
-            const uint8_t* nulls = src.has_nulls ? src.nulls.as<uint8_t>() : nullptr;
-            o.has_nulls = nulls != nullptr;
-            if (src.varwidth) {
-                int32_t* lens = static_cast<int32_t*>(o.offsets.ensure((size_t)(count + 1) * 4));
-                launch_varwidth_lengths(pos, count, src.offsets.as<int32_t>(), nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, count, ctl_ + 2, scan_temp_.ensure(scan_temp_bytes(count)), s);
-                PA_HIP(hipMemcpyAsync(h_ctl_ + 2, ctl_ + 2, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                const int32_t bytes = h_ctl_[2];
-                launch_varwidth_copy(pos, count, src.offsets.as<int32_t>(), src.values.as<uint8_t>(), nulls, lens,
-                                     static_cast<uint8_t*>(o.values.ensure((size_t)(bytes > 0 ? bytes : 1))), ctl_ + 2, s);
-            }
-            else {
-                const int w = type_width(src.type);
-                launch_gather_flat(src.values.ptr(), w, pos, count, o.values.ensure((size_t)count * w), s);
-            }
-            if (nulls) launch_gather_nulls(nulls, pos, count, static_cast<uint8_t*>(o.nulls.ensure((size_t)count)), s);
-        }
+        for (int c : ls_->output_channels) gather_.copy_positions(ls_->cols[c].view(), pos, count, out_cols_[oc++], s);
         publish_output(out_cols_, count, output_mem_, s, out, out_storage_);
         return true;
     }
@@ -1160,10 +1118,8 @@ private:
     std::vector<int32_t> probe_output_types_;
     int output_mem_ = PA_MEM_HOST;
     bool done_ = false;
-    DevBuf ctl_buf_, part_, pos_, counts_, part_temp_, scan_temp_;
-    PinnedBuf h_ctl_buf_;
-    int32_t* ctl_ = nullptr;
-    int32_t* h_ctl_ = nullptr;
+    DevBuf part_, pos_, counts_, part_temp_;
+    PositionGather gather_;
     std::vector<OutColumn> out_cols_;
     std::vector<pa_column> out_storage_;
 };

@@ -224,14 +224,14 @@ public:
             else continue;
             produced[j] = true;
         }
-        store_.gather_sorted(perm, n, outs, &produced, out_cols_, scan_temp_, static_cast<int32_t*>(total_word_.ensure(4)), s);
+        store_.gather_sorted(perm, n, outs, &produced, out_cols_, gather_, s);
         publish_output(out_cols_, (int32_t)n, output_mem_, s, out, out_storage_);
         return true;
     }
 
     int64_t memory_bytes() override
     {
-        return (int64_t)store_.bytes();
+        return (int64_t)(store_.bytes() + gather_.bytes());
     }
 
 private:
@@ -252,7 +252,8 @@ private:
     int32_t output_mem_ = PA_MEM_HOST;
     bool finishing_ = false, output_done_ = false;
     RowSorter sorter_;
-    DevBuf payload_out_[PA_SORT_MAX_PAYLOAD], scan_temp_, total_word_;   // (total_word_: gather_sorted's VARCHAR byte total)
+    DevBuf payload_out_[PA_SORT_MAX_PAYLOAD];
+    PositionGather gather_;
     std::vector<OutColumn> out_cols_;
     std::vector<pa_column> out_storage_;
 };

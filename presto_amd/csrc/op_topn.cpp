@@ -15,6 +15,7 @@
 
 #include "keyed_operator.hpp"
 #include "operator.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 #include "topn_kernels.hpp"
 
@@ -322,20 +323,12 @@ private:
                 hc.values.insert(hc.values.end(), landed + p.at, landed + p.at + p.bytes);
                 continue;
             }
-            // VARCHAR: lengths -> exclusive scan -> byte copy (as FilterAndProject's copyPositions), or the whole block
+            // VARCHAR: copyPositions of the values (the NULL flags went with the side buffer), or the whole block
             std::vector<uint8_t> raw_off, raw_bytes;
             if (positions) {
-                int32_t* lens = static_cast<int32_t*>(var_off_.ensure((size_t)(count + 1) * 4));
-                int32_t* total = static_cast<int32_t*>(counts_.ensure(64)) + 8;
-                launch_varwidth_lengths(positions, count, col.offsets, col.nulls, lens, s);
-                launch_exclusive_scan_i32(lens, lens, count, total, scan_temp_.ensure(scan_temp_bytes(count)), s);
-                int32_t h_total = 0;
-                PA_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                uint8_t* bytes = static_cast<uint8_t*>(var_bytes_.ensure((size_t)(h_total > 0 ? h_total : 1)));
-                launch_varwidth_copy(positions, count, col.offsets, static_cast<const uint8_t*>(col.values), col.nulls, lens, bytes, total, s);
-                fetch(lens, (size_t)(count + 1) * 4, raw_off);
-                fetch(bytes, (size_t)h_total, raw_bytes);
+                const int32_t h_total = varchar_gather_.copy_varwidth(col, positions, (int32_t)count, var_off_, var_bytes_, s);
+                fetch(var_off_.ptr(), (size_t)(count + 1) * 4, raw_off);
+                fetch(var_bytes_.ptr(), (size_t)h_total, raw_bytes);
             }
             else {
                 fetch(col.offsets, (size_t)(n + 1) * 4, raw_off);
@@ -522,6 +515,7 @@ private:
     bool finishing_ = false, output_done_ = false;
     uint64_t threshold_ = ~0ULL;  // rows whose first-channel key is above it cannot be among the N best
     DevBuf keys_, part_, pos_, counts_, part_temp_, select_temp_, gather_, var_off_, var_bytes_, scan_temp_;
+    PositionGather varchar_gather_;
     DevBuf keys2_, state_, tie_rank_;  // refine_ties
     PinnedBuf land_, side_land_, h_hist_buf_, found_land_;
     uint32_t* h_hist_ = nullptr;

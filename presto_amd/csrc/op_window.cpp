@@ -251,7 +251,7 @@ public:
         int32_t* peer_index = part_index + n;
         int32_t* part_start = static_cast<int32_t*>(starts_.ensure(((size_t)n + 1) * 8));
         int32_t* peer_start = part_start + (n + (size_t)1);
-        int32_t* words = static_cast<int32_t*>(words_.ensure(64));   // [partition flags set, peer flags set, error, -, an output VARCHAR's bytes]
+        int32_t* words = static_cast<int32_t*>(words_.ensure(64));   // [partition flags set, peer flags set, error]
         void* scan_temp = scan_temp_.ensure(scan_temp_bytes(n));
         PA_HIP(hipMemsetAsync(part_flag, 0, (size_t)n * 8, s));
         PA_HIP(hipMemsetAsync(words, 0, 64, s));
@@ -339,7 +339,7 @@ public:
         PA_REQUIRE((h_words[2] & kWindowErrorLagOffset) == 0, PA_ERR_INVALID_ARGUMENT, "Offset must be at least 0");
         PA_REQUIRE((h_words[2] & kWindowErrorNthOffset) == 0, PA_ERR_INVALID_ARGUMENT, "Offset must be at least 1");
         // the output channels in sorted order (PagesIndex.appendTo)
-        held_.gather_sorted(perm, n, output_channels_, nullptr, out_cols_, scan_temp_, words + 4, s);
+        held_.gather_sorted(perm, n, output_channels_, nullptr, out_cols_, gather_, s);
         publish_output(out_cols_, n, output_mem_, s, out, storage_);
         return true;
     }
@@ -349,7 +349,7 @@ public:
     // the rows held, and the scratch of the sort and the passes while it is allocated
     int64_t memory_bytes() override
     {
-        size_t b = stager_.bytes() + sorter_.bytes() + flags_.capacity() + starts_.capacity() + words_.capacity() + scan_temp_.capacity() + aggregates_.capacity();
+        size_t b = stager_.bytes() + sorter_.bytes() + flags_.capacity() + starts_.capacity() + words_.capacity() + scan_temp_.capacity() + aggregates_.capacity() + gather_.bytes();
         return (int64_t)(b + held_.bytes());
     }
 
@@ -442,6 +442,7 @@ private:
     HeldRows held_;
     RowSorter sorter_;
     DevBuf flags_, starts_, words_, scan_temp_;
+    PositionGather gather_;
     DevBuf aggregates_;            // the aggregates' sorted arguments, scanned states and tile states
     std::vector<OutColumn> out_cols_;
     std::vector<pa_column> storage_;

@@ -1,6 +1,6 @@
 """Operator micro-benchmarks on device-resident pages (dev tool; numbers quoted in DESIGN.md):
 FilterAndProject (Q6 shape), HashAggregation at several cardinalities (BenchmarkGroupByHash shape), hash join build /
-probe (BenchmarkHashBuildAndJoinOperators shape).  rows/s = input rows / wall time including the final sync."""
+probe (BenchmarkHashBuildAndJoinOperators shape); `varchar`: a VARCHAR output channel through FilterAndProject and LookupJoin.  rows/s = input rows / wall time including the final sync."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -197,6 +197,49 @@ if "vagg" in which:
         dt = timeit(run, reps=3)
         print("HashAggregation VARCHAR(25) key %8d groups: %.3g rows/s (%.1f GB/s of the 36 B/row inputs), %d groups out; wall %.2f ms, fused kernels %.2f ms"
               % (groups, rows / dt, rows * 36 / dt / 1e9, run(), dt * 1e3, run.kernel_ms))
+
+if "varchar" in which:
+    # a VARCHAR(24) output channel ("Customer#%09d" + padding) through Block.copyPositions: FilterAndProject with half the rows selected,
+    # and LookupJoin with the strings on the build side (one probe row in two matches)
+    rows, nb, width = 1 << 22, 1 << 20, 24
+    g = torch.Generator(device="cuda").manual_seed(6)
+
+    def names(ids):
+        n = ids.numel()
+        digits = torch.stack([(ids // 10 ** k) % 10 + 48 for k in range(8, -1, -1)], dim=1).to(torch.uint8)
+        text = torch.cat([torch.tensor(list(b"Customer#"), dtype=torch.uint8, device="cuda").expand(n, 9), digits,
+                          torch.full((n, width - 18), 120, dtype=torch.uint8, device="cuda")], dim=1).contiguous()
+        offs = (torch.arange(n + 1, dtype=torch.int64, device="cuda") * width).to(torch.int32)
+        return Block(abi.VARCHAR, abi.VARWIDTH, n, values=DeviceBuffer(text.data_ptr(), text.numel(), text), offsets=DeviceBuffer(offs.data_ptr(), offs.numel() * 4, offs))
+    ids = torch.randint(0, 1 << 30, (rows,), dtype=torch.int64, device="cuda", generator=g)
+    flag = torch.randint(0, 2, (rows,), dtype=torch.int64, device="cuda", generator=g)
+    page = Page([names(ids), dev_block(abi.BIGINT, flag)], rows, abi.MEM_DEVICE)
+    def run():
+        op = FilterAndProjectOperator([abi.VARCHAR, abi.BIGINT], field(1, abi.BIGINT).eq(1), [field(0, abi.VARCHAR), field(1, abi.BIGINT)], output_mem=abi.MEM_DEVICE)
+        op.addInput(page)
+        n = op.getOutput().position_count
+        op.finish()
+        op.close()
+        return n
+    dt = timeit(run)
+    print("FilterAndProject VARCHAR(24) output, %d rows, one in two selected: %.4g rows/s, %d rows out" % (rows, rows / dt, run()))
+    bkeys = torch.randperm(nb, device="cuda", generator=g).to(torch.int64) * 2
+    build = Page([dev_block(abi.BIGINT, bkeys), names(bkeys)], nb, abi.MEM_DEVICE)
+    pkeys = torch.randint(0, nb * 2, (rows,), dtype=torch.int64, device="cuda", generator=g)
+    probe = Page([dev_block(abi.BIGINT, pkeys)], rows, abi.MEM_DEVICE)
+    bridge = LookupSourceFactory()
+    b = HashBuilderOperator(bridge, [abi.BIGINT, abi.VARCHAR], [0], [1], expected_positions=nb)
+    b.addInput(build)
+    b.finish()
+    def run():
+        j = LookupJoinOperator(bridge, [abi.BIGINT], [0], [0], output_mem=abi.MEM_DEVICE)
+        j.addInput(probe)
+        out = j.getOutput()
+        j.finish()
+        j.close()
+        return out.position_count
+    dt = timeit(run)
+    print("LookupJoin VARCHAR(24) build output, %d build rows, %d probe rows: %.4g rows/s, %d matches" % (nb, rows, rows / dt, run()))
 
 if "join" in which:
     g = torch.Generator(device="cuda").manual_seed(2)
