@@ -72,6 +72,10 @@ Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc&
             if (it != proj_of_build_col.end()) return it->second;
             const int32_t t = ls.cols[col].type;
             PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "VARCHAR build columns are not read by the fused probe");
+            // refused here, when the operator is created, so that such a join-aggregation runs as the chain: probe_build_loads has no
+            // load for any other type, and would only say so when the first page generates the kernel
+            PA_REQUIRE(t == PA_BIGINT || t == PA_INTEGER || t == PA_DATE || t == PA_DOUBLE || t == PA_BOOLEAN, PA_ERR_NOT_SUPPORTED,
+                       "the fused probe reads BIGINT / INTEGER / DATE / DOUBLE / BOOLEAN build columns");
             PA_REQUIRE((int)js->build_cols.size() < kMaxBuildChannels, PA_ERR_NOT_SUPPORTED, "the fused probe reads at most 8 build columns");
             const int v = (int)js->build_cols.size();
             js->build_cols.push_back(col);
