@@ -427,6 +427,54 @@ typedef struct pa_hash_semi_join_desc {  /* HashSemiJoinOperator.createOperatorF
     void* stream;
 } pa_hash_semi_join_desc;
 
+/* NestedLoopBuildOperator + NestedLoopJoinOperator (join/NestedLoopBuildOperator.java, join/NestedLoopJoinOperator.java,
+ * NestedLoopJoinPagesBuilder.java): what LocalExecutionPlanner plans for a JoinNode without equi-criteria -- every CROSS JOIN, every
+ * uncorrelated scalar subquery, every inner join over an inequality alone.  The FilterAndProject the planner puts above such a join may
+ * be given to the join as `filter`: the product is then never materialised.
+ *   Result.  With the M build rows in arrival order (pages in arrival order), every probe page emits one row per pair (i, j), i a row
+ *     of the page and j in [0, M), for which the filter is absent or TRUE (a filter value of SQL NULL counts as false).  The order is
+ *     PROBE-MAJOR: i ascending, inside one i, j ascending.  Columns: the probe output channels of row i, then the build output channels
+ *     of row j, as flat copies of the bytes (-0.0, NaN payloads, BOOLEAN bytes and all 16 bytes of a long decimal pass unchanged).  The
+ *     output rows are a function of the two input row sequences alone: not of page boundaries on either side, of host or device pages,
+ *     of their encodings, or of the run.  (The reference emits the same multiset in another order -- per (probe page, build page)
+ *     pair, one page per row of the smaller side, as RLE blocks.  No consumer may rely on the order of a cross join; probe-major is
+ *     what this library promises.)  How the output is cut into pages is not part of the contract, except that no page holds more than
+ *     2^30 rows (PRESTO_AMD_JOIN_MAX_OUTPUT_ROWS, as for pa_lookup_join_create): a probe page whose pairs exceed the bound comes out as
+ *     several pages, a single probe row whose pairs exceed it is cut between build rows.  M = 0 or an empty probe page gives no page.
+ *   Filter.  A BOOLEAN expression over one pair, numbered exactly as pa_lookup_join_desc.filter: [0, B) = the build page's channels,
+ *     [B, B + probe_channel_count) = the probe page's.  It accepts what the filter of pa_filter_project_desc accepts and refuses what
+ *     that refuses, with the same status; a non-BOOLEAN root or a channel out of range is PA_ERR_INVALID_ARGUMENT.  It is evaluated on
+ *     EVERY pair of the product, as the reference's FilterAndProject above the join does, so an evaluation error (division by zero,
+ *     integer overflow, decimal casts) is raised whatever the other conjuncts would have dropped, beyond the short-circuit rules of
+ *     AND / OR / IF.  The failing call is the pa_op_get_output that would have delivered the pairs of that part of the product; pages
+ *     delivered earlier stand, and the operator can still be closed.
+ *   Types.  Every channel of either side: BIGINT, INTEGER, DATE, DOUBLE, REAL, BOOLEAN, VARCHAR, PA_DECIMAL, PA_LONG_DECIMAL; PA_ROW
+ *     anywhere, no output channel at all (both counts 0: the reference's position-count-only pages are not modelled) and more than 64
+ *     channels on both sides together are PA_ERR_NOT_SUPPORTED.  Negative counts, NULL arrays behind non-zero counts, channel indices out
+ *     of range, a bad output_mem and unknown types are PA_ERR_INVALID_ARGUMENT; an invalid argument is reported before a refusal, and
+ *     both before the device is asked for (PA_ERR_NO_DEVICE).
+ *   Limits.  More than INT32_MAX build rows, the HBM budget, or 2 GiB or more of VARCHAR bytes in one output column of one page:
+ *     PA_ERR_INSUFFICIENT_RESOURCES. */
+typedef struct pa_nested_loop_build_desc {   /* NestedLoopBuildOperatorFactory */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere; NULL = all 0 */
+    void* stream;
+} pa_nested_loop_build_desc;
+
+typedef struct pa_nested_loop_join_desc {    /* NestedLoopJoinOperatorFactory(probeTypes, probeChannels, buildChannels) */
+    int32_t probe_channel_count;
+    const int32_t* probe_types;
+    const int32_t* probe_type_params;    /* may be NULL */
+    int32_t probe_output_channel_count;
+    const int32_t* probe_output_channels;
+    int32_t build_output_channel_count;
+    const int32_t* build_output_channels;
+    const pa_expr* filter;               /* NULL: the plain product */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_nested_loop_join_desc;
+
 /* MarkDistinctOperator + DistinctLimitOperator: `count(DISTINCT x)` / `SELECT DISTINCT ... LIMIT n`, planned by
  * LocalExecutionPlanner.visitMarkDistinct (:1540) and visitDistinctLimit (:1455) (MarkDistinctOperator.java, MarkDistinctHash.java:52-69,
  * DistinctLimitOperator.java:175-223), both over GroupByHash.getGroupIds.  A row is NEW when no earlier row -- of an earlier page, or at
@@ -941,6 +989,26 @@ int32_t pa_channel_set_destroy(pa_channel_set* set);
 int32_t pa_channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
 int32_t pa_set_builder_create(const pa_set_builder_desc* desc, pa_channel_set* set, pa_operator** out);
 int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_set* set, pa_operator** out);
+/* Nested-loop join (pa_nested_loop_build_desc above).  The handle (NestedLoopJoinBridge / NestedLoopJoinPages), its builder and its
+ * join operators may be closed / destroyed in any order.
+ * Builder: needs input until finish, which publishes the rows; it never produces output; empty pages are accepted.  One builder per
+ * handle (a second: PA_ERR_ILLEGAL_STATE).  It holds the build channels that the join operators created before its first page with
+ * rows read in their filter or output -- every channel when there is none yet; a channel nobody reads is not held.  (A join
+ * operator created later that reads a channel not held is PA_ERR_ILLEGAL_STATE.)  Dictionary and RLE blocks are held flat.
+ * Join operator: the builder must already have been created on the handle -- the join needs the build types to check and compile its
+ * filter -- else PA_ERR_ILLEGAL_STATE.  pa_op_is_blocked is 1 and needs_input 0 until the rows are published (add_input before:
+ * PA_ERR_ILLEGAL_STATE); then needs_input = not finishing and no output pending from the current probe page, is_finished = finishing
+ * and nothing pending.  Several join operators may share one handle.
+ * pa_op_memory_bytes: the builder reports the rows held, the join its position lists and its staged probe page.
+ * PRESTO_AMD_NL_VARIANT=0|1, read when a join operator is created, forces the lane mapping of its pair kernels (0: lanes over probe
+ * rows, 1: lanes over build rows); the output is byte-identical under either. */
+typedef struct pa_nested_loop_pages pa_nested_loop_pages;
+int32_t pa_nested_loop_pages_create(pa_nested_loop_pages** out);
+int32_t pa_nested_loop_pages_destroy(pa_nested_loop_pages* pages);
+/* the build rows; PA_ERR_ILLEGAL_STATE before the builder finished */
+int32_t pa_nested_loop_pages_rows(pa_nested_loop_pages* pages, int64_t* rows);
+int32_t pa_nested_loop_build_create(const pa_nested_loop_build_desc* desc, pa_nested_loop_pages* pages, pa_operator** out);
+int32_t pa_nested_loop_join_create(const pa_nested_loop_join_desc* desc, pa_nested_loop_pages* pages, pa_operator** out);
 /* MarkDistinct / DistinctLimit (pa_mark_distinct_desc above). */
 int32_t pa_mark_distinct_create(const pa_mark_distinct_desc* desc, pa_operator** out);
 int32_t pa_distinct_limit_create(const pa_distinct_limit_desc* desc, pa_operator** out);
@@ -1178,6 +1246,11 @@ int64_t pa_codegen_fused_join_probe(const pa_fused_join_desc* desc, const pa_has
 int64_t pa_codegen_compile_fused_join_probe(const pa_fused_join_desc* desc, const pa_hash_builder_desc* build);
 int64_t pa_codegen_filter_project(const pa_filter_project_desc* desc, char* buf, int64_t buf_size, char* key);
 int64_t pa_codegen_compile_filter_project(const pa_filter_project_desc* desc);
+/* the pair kernels (count and emit form) of a nested-loop join with a filter over a build side shaped as `build` describes.  variant
+ * bit 0: the lane mapping (0 lanes over probe rows, 1 lanes over build rows); bit 1: every channel the filter reads carries NULL flags
+ * (else none does).  A join without a filter has no generated kernel: PA_ERR_INVALID_ARGUMENT. */
+int64_t pa_codegen_nested_loop(const pa_nested_loop_join_desc* desc, const pa_nested_loop_build_desc* build, int32_t variant, char* buf, int64_t buf_size);
+int64_t pa_codegen_compile_nested_loop(const pa_nested_loop_join_desc* desc, const pa_nested_loop_build_desc* build, int32_t variant);
 
 #ifdef __cplusplus
 }

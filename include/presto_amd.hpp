@@ -471,6 +471,85 @@ inline std::unique_ptr<Operator> createHashSemiJoinOperator(ChannelSetSupplier& 
     return std::make_unique<Operator>(h);
 }
 
+// NestedLoopJoinBridge / NestedLoopJoinPages: the rows a NestedLoopBuildOperator publishes and its NestedLoopJoinOperators read
+class NestedLoopJoinBridge {
+public:
+    NestedLoopJoinBridge() { check(pa_nested_loop_pages_create(&h_)); }
+    NestedLoopJoinBridge(const NestedLoopJoinBridge&) = delete;
+    NestedLoopJoinBridge& operator=(const NestedLoopJoinBridge&) = delete;
+    ~NestedLoopJoinBridge()
+    {
+        if (h_) pa_nested_loop_pages_destroy(h_);
+    }
+    pa_nested_loop_pages* handle() { return h_; }
+    // the build rows, once the builder finished
+    int64_t rows()
+    {
+        int64_t n = 0;
+        check(pa_nested_loop_pages_rows(h_, &n));
+        return n;
+    }
+
+private:
+    pa_nested_loop_pages* h_ = nullptr;
+};
+
+// NestedLoopBuildOperatorFactory: createOperator before the join operators' (they need the build types)
+struct NestedLoopBuildOperatorFactory {
+    std::vector<int32_t> sourceTypes, typeParams;
+
+    explicit NestedLoopBuildOperatorFactory(std::vector<int32_t> sourceTypes, std::vector<int32_t> typeParams = {})
+        : sourceTypes(std::move(sourceTypes)), typeParams(std::move(typeParams))
+    {
+    }
+
+    std::unique_ptr<Operator> createOperator(NestedLoopJoinBridge& bridge) const
+    {
+        pa_nested_loop_build_desc d{};
+        d.input_channel_count = (int32_t)sourceTypes.size();
+        d.input_types = sourceTypes.data();
+        d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        pa_operator* h = nullptr;
+        check(pa_nested_loop_build_create(&d, bridge.handle(), &h));
+        return std::make_unique<Operator>(h);
+    }
+};
+
+// NestedLoopJoinOperatorFactory(probeTypes, probeChannels, buildChannels) with the filter of the FilterAndProject above the join over
+// [build page channels, probe page channels] (null: the plain product); one row per surviving pair, probe-major
+struct NestedLoopJoinOperatorFactory {
+    std::vector<int32_t> probeTypes, probeChannels, buildChannels;
+    Expr filter;
+    int32_t outputMem = PA_MEM_HOST;
+    std::vector<int32_t> typeParams;
+
+    NestedLoopJoinOperatorFactory(std::vector<int32_t> probeTypes, std::vector<int32_t> probeChannels, std::vector<int32_t> buildChannels, Expr filter = nullptr,
+                                  int32_t outputMem = PA_MEM_HOST)
+        : probeTypes(std::move(probeTypes)), probeChannels(std::move(probeChannels)), buildChannels(std::move(buildChannels)), filter(std::move(filter)),
+          outputMem(outputMem)
+    {
+    }
+
+    std::unique_ptr<Operator> createOperator(NestedLoopJoinBridge& bridge) const
+    {
+        std::unique_ptr<SerializedExpression> f;
+        if (filter) f = std::make_unique<SerializedExpression>(filter);
+        pa_nested_loop_join_desc d{};
+        d.probe_channel_count = (int32_t)probeTypes.size();
+        d.probe_types = probeTypes.data();
+        d.probe_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        d.probe_output_channel_count = (int32_t)probeChannels.size();
+        d.probe_output_channels = probeChannels.data();
+        d.build_output_channel_count = (int32_t)buildChannels.size();
+        d.build_output_channels = buildChannels.data();
+        d.filter = f ? f->get() : nullptr;
+        d.output_mem = outputMem;
+        pa_operator* h = nullptr;
+        check(pa_nested_loop_join_create(&d, bridge.handle(), &h));
+        return std::make_unique<Operator>(h);
+    }
+};
+
 // MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel): the input page with a BOOLEAN column appended, true on
 // the first row that carries a key
 inline std::unique_ptr<Operator> createMarkDistinctOperator(const std::vector<int32_t>& inputTypes, const std::vector<int32_t>& distinctChannels,

@@ -72,6 +72,15 @@ final class GpuNative
     static native long createSetBuilder(long channelSet, int[] inputTypes, int[] typeParams, int setChannel, int hashChannel, int expectedPositions);
     /** HashSemiJoinOperator.createOperatorFactory(probeTypes, probeJoinChannel, probeJoinHashChannel): the probe page plus a BOOLEAN mark. */
     static native long createHashSemiJoin(long channelSet, int[] probeTypes, int[] typeParams, int probeJoinChannel, int probeHashChannel, int outputMem);
+    /** NestedLoopJoinBridge: the pa_nested_loop_pages a nested-loop join's builder and join operators share (GpuNestedLoopJoin). */
+    static native long createNestedLoopPages();
+    static native void destroyNestedLoopPages(long nestedLoopPages);
+    /** NestedLoopBuildOperatorFactory; created before the join operators of the same pages (they need the build types); typeParams may be null. */
+    static native long createNestedLoopBuild(long nestedLoopPages, int[] inputTypes, int[] typeParams);
+    /** NestedLoopJoinOperatorFactory(probeTypes, probeChannels, buildChannels); filterExpression: over [build page channels, probe page
+     *  channels], 0 = the plain product.  One row per surviving pair, probe-major. */
+    static native long createNestedLoopJoin(long nestedLoopPages, int[] probeTypes, int[] typeParams, int[] probeOutputChannels, int[] buildOutputChannels,
+            long filterExpression, int outputMem);
     /** MarkDistinctOperatorFactory(sourceTypes, markDistinctChannels, hashChannel): the input page plus a BOOLEAN mark (GpuDistinct). */
     static native long createMarkDistinct(int[] inputTypes, int[] typeParams, int[] distinctChannels, int hashChannel, int expectedDistinct, int outputMem);
     /** DistinctLimitOperatorFactory(sourceTypes, distinctChannels, limit, hashChannel): the first `limit` distinct keys in arrival order. */

@@ -8,6 +8,7 @@ import io.trino.operator.join.LookupSourceFactory;
 import io.trino.spi.type.Type;
 import io.trino.spiller.PartitioningSpillerFactory;
 import io.trino.sql.planner.plan.PlanNodeId;
+import io.trino.sql.relational.RowExpression;
 import io.trino.type.BlockTypeOperators;
 
 import java.util.ArrayList;
@@ -99,6 +100,18 @@ public final class GpuOperatorFactories
         }
         return lookupJoin(operatorId, planNodeId, bridge, FULL_OUTER, false, probeTypes, probeJoinChannel, probeHashChannel, probeOutputChannels,
                 hasFilter ? FILTERS.get(lookupSourceFactory) : 0L);
+    }
+
+    /**
+     * A JoinNode without equi-criteria (LocalExecutionPlanner.createNestedLoopJoin: `new NestedLoopBuildOperatorFactory(...)` in the build
+     * pipeline, `new NestedLoopJoinOperatorFactory(...)` in the probe pipeline): not a method of OperatorFactories, so the planner hook
+     * calls it next to them.  filterAbove = the filter of the FilterAndProject that follows the join in the probe pipeline, if any; see
+     * GpuNestedLoopJoin for what becomes of it.  Optional.empty(): keep the reference factories.
+     */
+    public static Optional<GpuNestedLoopJoin> nestedLoopJoin(int buildOperatorId, PlanNodeId buildNodeId, List<Type> buildTypes, int joinOperatorId,
+            PlanNodeId joinNodeId, List<Type> probeTypes, List<Integer> probeChannels, List<Integer> buildChannels, Optional<RowExpression> filterAbove)
+    {
+        return GpuNestedLoopJoin.create(buildOperatorId, buildNodeId, buildTypes, joinOperatorId, joinNodeId, probeTypes, probeChannels, buildChannels, filterAbove);
     }
 
     private static OperatorFactory lookupJoin(int operatorId, PlanNodeId planNodeId, long bridge, int joinType, boolean outputSingleMatch, List<Type> probeTypes,

@@ -50,10 +50,20 @@ final class RowExpressionSerializer
     private final List<byte[]> strings = new ArrayList<>();
     private final List<Integer> args = new ArrayList<>();
 
+    private int[] channelMap;   // input channel -> channel written (null: as it is; -1: no counterpart)
+
     /** Returns the native handle of the flattened tree (GpuNative.freeExpression releases it). */
     static long serialize(RowExpression expression)
     {
+        return serialize(expression, null);
+    }
+
+    /** The same with every input reference renumbered through channelMap: an expression over one page layout moved onto another
+     *  (GpuNestedLoopJoin: the join's output layout -> the (build row, probe row) pair layout). */
+    static long serialize(RowExpression expression, int[] channelMap)
+    {
         RowExpressionSerializer s = new RowExpressionSerializer();
+        s.channelMap = channelMap;
         int root = expression.accept(s, null);
         int n = s.nodes.size();
         int[][] columns = new int[8][n];
@@ -222,7 +232,14 @@ final class RowExpressionSerializer
     @Override
     public Integer visitInputReference(InputReferenceExpression reference, Void context)
     {
-        return add(INPUT_REF, 0, reference.getType(), reference.getField(), false, List.of(), 0, 0, null);
+        int field = reference.getField();
+        if (channelMap != null) {
+            if (field < 0 || field >= channelMap.length || channelMap[field] < 0) {
+                throw new UnsupportedOnDevice("input channel " + field + " has no counterpart in the target layout");
+            }
+            field = channelMap[field];
+        }
+        return add(INPUT_REF, 0, reference.getType(), field, false, List.of(), 0, 0, null);
     }
 
     @Override

@@ -544,6 +544,52 @@ JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createHashSemiJoin(JNIEnv* e
     return (jlong)(intptr_t)op;
 }
 
+/* LocalExecutionPlanner.createNestedLoopJoin: NestedLoopBuildOperatorFactory + NestedLoopJoinOperatorFactory sharing one
+ * pa_nested_loop_pages (the NestedLoopJoinBridge); the builder is created before the join operators.  filter = a serialised expression
+ * over [build page channels, probe page channels] or 0 for the plain product; typeParams may be null. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createNestedLoopPages(JNIEnv* env, jclass c)
+{
+    pa_nested_loop_pages* pages = 0;
+    int32_t rc = pa_nested_loop_pages_create(&pages);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)pages;
+}
+JNIEXPORT void JNICALL Java_io_trino_gpu_GpuNative_destroyNestedLoopPages(JNIEnv* env, jclass c, jlong h) { CHECK(pa_nested_loop_pages_destroy((pa_nested_loop_pages*)(intptr_t)h)); }
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createNestedLoopBuild(JNIEnv* env, jclass c, jlong pages, jintArray inputTypes, jintArray typeParams)
+{
+    jsize n, np_ = 0;
+    pa_nested_loop_build_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t* types = ints_of(env, inputTypes, &n);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    pa_operator* op = 0;
+    int32_t rc = pa_nested_loop_build_create(&d, (pa_nested_loop_pages*)(intptr_t)pages, &op);
+    free(params); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createNestedLoopJoin(JNIEnv* env, jclass c, jlong pages, jintArray probeTypes, jintArray typeParams,
+        jintArray probeOutputChannels, jintArray buildOutputChannels, jlong filter, jint outputMem)
+{
+    jsize n, np_ = 0, npo, nbo;
+    pa_nested_loop_join_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, probeTypes, &n), *po = ints_of(env, probeOutputChannels, &npo), *bo = ints_of(env, buildOutputChannels, &nbo);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.probe_channel_count = n; d.probe_types = types; d.probe_type_params = params && np_ == n ? params : 0;
+    d.probe_output_channel_count = npo; d.probe_output_channels = po; d.build_output_channel_count = nbo; d.build_output_channels = bo;
+    d.filter = filter ? &((native_expr*)(intptr_t)filter)->expr : 0;
+    d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_nested_loop_join_create(&d, (pa_nested_loop_pages*)(intptr_t)pages, &op);
+    free(params); free(bo); free(po); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
 /* LocalExecutionPlanner.visitMarkDistinct / visitDistinctLimit: MarkDistinctOperatorFactory / DistinctLimitOperatorFactory.  typeParams
  * may be null (all 0) or one VARCHAR(n) bound / PA_DECIMAL_PARAM per channel. */
 JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createMarkDistinct(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,

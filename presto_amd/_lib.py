@@ -61,6 +61,11 @@ def lib():
     L.pa_channel_set_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
     L.pa_set_builder_create.argtypes = [C.POINTER(abi.pa_set_builder_desc), vp, C.POINTER(vp)]
     L.pa_hash_semi_join_create.argtypes = [C.POINTER(abi.pa_hash_semi_join_desc), vp, C.POINTER(vp)]
+    L.pa_nested_loop_pages_create.argtypes = [C.POINTER(vp)]
+    L.pa_nested_loop_pages_destroy.argtypes = [vp]
+    L.pa_nested_loop_pages_rows.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.pa_nested_loop_build_create.argtypes = [C.POINTER(abi.pa_nested_loop_build_desc), vp, C.POINTER(vp)]
+    L.pa_nested_loop_join_create.argtypes = [C.POINTER(abi.pa_nested_loop_join_desc), vp, C.POINTER(vp)]
     L.pa_mark_distinct_create.argtypes = [C.POINTER(abi.pa_mark_distinct_desc), C.POINTER(vp)]
     L.pa_distinct_limit_create.argtypes = [C.POINTER(abi.pa_distinct_limit_desc), C.POINTER(vp)]
     L.pa_distinct_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -113,6 +118,10 @@ def lib():
     L.pa_codegen_filter_project.restype = C.c_int64
     L.pa_codegen_compile_filter_project.argtypes = [C.POINTER(abi.pa_filter_project_desc)]
     L.pa_codegen_compile_filter_project.restype = C.c_int64
+    L.pa_codegen_nested_loop.argtypes = [C.POINTER(abi.pa_nested_loop_join_desc), C.POINTER(abi.pa_nested_loop_build_desc), C.c_int32, C.c_char_p, C.c_int64]
+    L.pa_codegen_nested_loop.restype = C.c_int64
+    L.pa_codegen_compile_nested_loop.argtypes = [C.POINTER(abi.pa_nested_loop_join_desc), C.POINTER(abi.pa_nested_loop_build_desc), C.c_int32]
+    L.pa_codegen_compile_nested_loop.restype = C.c_int64
     L.pa_filter_project_selected_positions.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.pa_lookup_join_match_pairs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32)]
     L.pa_lookup_source_tables.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(vp), C.POINTER(C.c_int32)]

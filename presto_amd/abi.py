@@ -325,6 +325,30 @@ class pa_hash_semi_join_desc(C.Structure):
     ]
 
 
+class pa_nested_loop_build_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("stream", C.c_void_p),
+    ]
+
+
+class pa_nested_loop_join_desc(C.Structure):
+    _fields_ = [
+        ("probe_channel_count", C.c_int32),
+        ("probe_types", C.POINTER(C.c_int32)),
+        ("probe_type_params", C.POINTER(C.c_int32)),
+        ("probe_output_channel_count", C.c_int32),
+        ("probe_output_channels", C.POINTER(C.c_int32)),
+        ("build_output_channel_count", C.c_int32),
+        ("build_output_channels", C.POINTER(C.c_int32)),
+        ("filter", C.POINTER(pa_expr)),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_mark_distinct_desc(C.Structure):
     _fields_ = [
         ("input_channel_count", C.c_int32),

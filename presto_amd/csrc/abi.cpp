@@ -612,6 +612,47 @@ int32_t pa_hash_semi_join_create(const pa_hash_semi_join_desc* desc, pa_channel_
     });
 }
 
+// ---- nested-loop join ----
+int32_t pa_nested_loop_pages_create(pa_nested_loop_pages** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "out is null");
+        *out = nested_loop_pages_new();
+        return PA_OK;
+    });
+}
+int32_t pa_nested_loop_pages_destroy(pa_nested_loop_pages* pages)
+{
+    return guarded([&]() -> int32_t {
+        if (pages) nested_loop_pages_delete(pages);
+        return PA_OK;
+    });
+}
+int32_t pa_nested_loop_pages_rows(pa_nested_loop_pages* pages, int64_t* rows)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(rows != nullptr, PA_ERR_INVALID_ARGUMENT, "rows is null");
+        *rows = nested_loop_pages_rows(pages);
+        return PA_OK;
+    });
+}
+int32_t pa_nested_loop_build_create(const pa_nested_loop_build_desc* desc, pa_nested_loop_pages* pages, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_nested_loop_build(desc, pages);
+        return PA_OK;
+    });
+}
+int32_t pa_nested_loop_join_create(const pa_nested_loop_join_desc* desc, pa_nested_loop_pages* pages, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_nested_loop_join(desc, pages);
+        return PA_OK;
+    });
+}
+
 // ---- MarkDistinct / DistinctLimit ----
 int32_t pa_mark_distinct_create(const pa_mark_distinct_desc* desc, pa_operator** out)
 {
@@ -1325,6 +1366,27 @@ int64_t pa_codegen_compile_filter_project(const pa_filter_project_desc* desc)
         std::string entry;
         std::string src = filter_project_source_for_desc(desc, &entry);
         size = (int64_t)jit_compile_only(src).size();
+        return PA_OK;
+    });
+    return rc < 0 ? rc : size;
+}
+
+int64_t pa_codegen_nested_loop(const pa_nested_loop_join_desc* desc, const pa_nested_loop_build_desc* build, int32_t variant, char* buf, int64_t buf_size)
+{
+    int64_t need = 0;
+    int32_t rc = guarded([&]() -> int32_t {
+        std::string tu = jit_translation_unit(nested_loop_source_for_desc(desc, build, variant));
+        need = (int64_t)tu.size() + 1;
+        if (buf && buf_size >= need) memcpy(buf, tu.c_str(), (size_t)need);
+        return PA_OK;
+    });
+    return rc < 0 ? rc : need;
+}
+int64_t pa_codegen_compile_nested_loop(const pa_nested_loop_join_desc* desc, const pa_nested_loop_build_desc* build, int32_t variant)
+{
+    int64_t size = 0;
+    int32_t rc = guarded([&]() -> int32_t {
+        size = (int64_t)jit_compile_only(nested_loop_source_for_desc(desc, build, variant)).size();
         return PA_OK;
     });
     return rc < 0 ? rc : size;

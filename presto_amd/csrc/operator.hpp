@@ -69,6 +69,12 @@ void channel_set_delete(pa_channel_set* set);
 void channel_set_stats(pa_channel_set* set, int64_t* size, int32_t* contains_null);
 pa_operator* make_set_builder(const pa_set_builder_desc* desc, pa_channel_set* set);
 pa_operator* make_hash_semi_join(const pa_hash_semi_join_desc* desc, pa_channel_set* set);
+// nested-loop join (op_nested_loop.cpp): the pages handle, NestedLoopBuildOperator and NestedLoopJoinOperator
+pa_nested_loop_pages* nested_loop_pages_new();
+void nested_loop_pages_delete(pa_nested_loop_pages* pages);
+int64_t nested_loop_pages_rows(pa_nested_loop_pages* pages);
+pa_operator* make_nested_loop_build(const pa_nested_loop_build_desc* desc, pa_nested_loop_pages* pages);
+pa_operator* make_nested_loop_join(const pa_nested_loop_join_desc* desc, pa_nested_loop_pages* pages);
 // MarkDistinctOperator / DistinctLimitOperator (op_distinct.cpp); distinct_stats: nextDistinctId and the table's slots
 pa_operator* make_mark_distinct(const pa_mark_distinct_desc* desc);
 pa_operator* make_distinct_limit(const pa_distinct_limit_desc* desc);
@@ -128,5 +134,7 @@ void lookup_source_shape_for_desc(const pa_hash_builder_desc* build, pa_lookup_s
 std::string filter_project_probe_source_for_desc(const pa_fused_join_desc* desc, const pa_hash_builder_desc* build);
 std::string fused_join_source_for_desc(const pa_fused_join_aggregation_desc* desc, const pa_hash_builder_desc* build, int variant, std::string* entry);
 std::string filter_project_source_for_desc(const pa_filter_project_desc* desc, std::string* entry);
+// the pair kernels of a nested-loop join's filter (variant bit 0: lane mapping, bit 1: the filter's channels carry NULL flags)
+std::string nested_loop_source_for_desc(const pa_nested_loop_join_desc* desc, const pa_nested_loop_build_desc* build, int variant);
 
 }  // namespace pa

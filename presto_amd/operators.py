@@ -810,6 +810,100 @@ def HashSemiJoinOperator(set_supplier, probe_types, probe_join_channel, probe_ha
     return HashSemiJoinOperatorFactory(probe_types, probe_join_channel, probe_hash_channel, output_mem, stream, type_params).createOperator(set_supplier)
 
 
+# ---- nested-loop join ------------------------------------------------------------------------------------
+class NestedLoopJoinBridge:
+    """NestedLoopJoinBridge / NestedLoopJoinPages: the rows a NestedLoopBuildOperator publishes and its NestedLoopJoinOperators read
+    (…/operator/join/NestedLoopJoinBridge.java, NestedLoopJoinPagesBuilder.java)."""
+
+    def __init__(self):
+        h = C.c_void_p()
+        check(lib().pa_nested_loop_pages_create(C.byref(h)))
+        self._h = h
+
+    def rows(self):
+        """The build rows (after the builder finished)."""
+        n = C.c_int64()
+        check(lib().pa_nested_loop_pages_rows(self._h, C.byref(n)))
+        return n.value
+
+    def destroy(self):
+        if self._h:
+            lib().pa_nested_loop_pages_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def nested_loop_build_desc(input_types, stream=None, type_params=None):
+    d = abi.pa_nested_loop_build_desc()
+    types = abi.int32_array(input_types)
+    keep = [types]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.stream = stream
+    return d, keep
+
+
+def nested_loop_join_desc(probe_types, probe_output_channels, build_output_channels, filter=None, output_mem=abi.MEM_HOST, stream=None,
+                          type_params=None):
+    d = abi.pa_nested_loop_join_desc()
+    types = abi.int32_array(probe_types)
+    pc, bc = abi.int32_array(probe_output_channels), abi.int32_array(build_output_channels)
+    keep = [types, pc, bc]
+    d.probe_channel_count = len(probe_types)
+    d.probe_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(probe_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.probe_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.probe_output_channel_count = len(probe_output_channels)
+    d.probe_output_channels = C.cast(pc, C.POINTER(C.c_int32))
+    d.build_output_channel_count = len(build_output_channels)
+    d.build_output_channels = C.cast(bc, C.POINTER(C.c_int32))
+    if filter is not None:
+        f, kf = serialize(filter)
+        d.filter = C.pointer(f)
+        keep += [f, kf]
+    d.output_mem = output_mem
+    d.stream = stream
+    return d, keep
+
+
+def NestedLoopBuildOperatorFactory(input_types, stream=None, type_params=None):
+    """NestedLoopBuildOperatorFactory (…/operator/join/NestedLoopBuildOperator.java)."""
+    d, keep = nested_loop_build_desc(input_types, stream, type_params)
+    return JoinOperatorFactory(lib().pa_nested_loop_build_create, d, keep)
+
+
+def NestedLoopBuildOperator(bridge, input_types, stream=None, type_params=None):
+    return NestedLoopBuildOperatorFactory(input_types, stream, type_params).createOperator(bridge)
+
+
+def NestedLoopJoinOperatorFactory(probe_types, probe_output_channels, build_output_channels, filter=None, output_mem=abi.MEM_HOST, stream=None,
+                                  type_params=None):
+    """NestedLoopJoinOperatorFactory(probeTypes, probeChannels, buildChannels) (…/operator/join/NestedLoopJoinOperator.java), with the
+    filter of the FilterAndProject above it as an expression over [build page channels, probe page channels] (the numbering of
+    LookupJoinOperator's filter), or None for the plain product.  The output is probe-major."""
+    d, keep = nested_loop_join_desc(probe_types, probe_output_channels, build_output_channels, filter, output_mem, stream, type_params)
+    return JoinOperatorFactory(lib().pa_nested_loop_join_create, d, keep)
+
+
+def NestedLoopJoinOperator(bridge, probe_types, probe_output_channels, build_output_channels, filter=None, output_mem=abi.MEM_HOST, stream=None,
+                           type_params=None):
+    return NestedLoopJoinOperatorFactory(probe_types, probe_output_channels, build_output_channels, filter, output_mem, stream,
+                                         type_params).createOperator(bridge)
+
+
 # ---- DISTINCT ----------------------------------------------------------------------------------------------
 def _distinct_desc(d, input_types, distinct_channels, hash_channel, expected_distinct, output_mem, stream, type_params):
     types = abi.int32_array(input_types)
