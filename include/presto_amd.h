@@ -518,6 +518,78 @@ typedef struct pa_distinct_limit_desc {  /* DistinctLimitOperatorFactory(sourceT
     void* stream;
 } pa_distinct_limit_desc;
 
+/* StreamingAggregationOperator: the aggregation over input that arrives grouped, planned by the streamable branch of
+ * LocalExecutionPlanner.visitAggregation with step SINGLE (StreamingAggregationOperator.java:171-367) -- the last operator of every
+ * decorrelated scalar subquery: AssignUniqueId -> LookupJoin (probe outer, which keeps probe order) -> this, grouped by the unique id.
+ *   Runs.  A run is a maximal sequence of consecutive input rows that are pairwise NOT DISTINCT on the 1 .. 8 group channels, under the
+ *     rule stated for MarkDistinct: both NULL counts as equal, for DOUBLE / REAL any NaN equals any NaN and -0.0 equals +0.0, VARCHAR
+ *     compares length and bytes, BOOLEAN zero / non-zero.  Runs continue across page boundaries; empty pages are skipped.  Key types:
+ *     BIGINT, INTEGER, DATE, DOUBLE, REAL, BOOLEAN, VARCHAR, PA_DECIMAL.
+ *   Output rows.  One row per run, in input order: the group columns with the bytes of the run's FIRST row, then the aggregates.  A run
+ *     is emitted once a row of another run has been seen, or at finish.
+ *   Output pages.  After pa_op_add_input at most one output page is pending: the runs that closed inside that page; no page if none
+ *     closed.  needs_input is 0 while a page is pending.  After finish, pa_op_get_output yields the open run as a page of one row.  No
+ *     input at all gives no output.
+ *   Aggregates.  The six pa_agg_fn with masks as everywhere (a NULL mask counts as false): count(*) and count; sum / avg over BIGINT,
+ *     INTEGER, DOUBLE, REAL; min / max over BIGINT, INTEGER, DATE, BOOLEAN, short DECIMAL, DOUBLE, REAL.  Result types as
+ *     pa_hash_aggregation_create's with step SINGLE: count BIGINT; sum the argument's type; avg DOUBLE (REAL for REAL); min / max the
+ *     argument's type, in Double.compare order for DOUBLE / REAL (-0.0 below +0.0, NaN above +infinity).  A run with no counted row gives
+ *     count 0 and NULL elsewhere.
+ *     sum over BIGINT is Math.addExact in row order: if any running prefix of a run's counted values leaves int64 -- also when it comes
+ *     back, also when the run spans pages -- the call that would hand out the run's row fails with PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE
+ *     (pa_op_add_input for a run that closes in the page, pa_op_get_output for the run that finish closes), nothing is emitted from then
+ *     on (is_finished is 1), and the operator can still be closed and destroyed.  sum over INTEGER adds in int64 and fails the same way
+ *     when the run's total does not fit the INTEGER column.  DOUBLE / REAL sum / avg and avg over integers add doubles pairwise, not in
+ *     row order: exact where every order of addition gives one answer, else within relative 1e-9 of the sequential sum.
+ *   Checks at creation, before the device is asked for, an invalid argument before a refusal.  PA_ERR_INVALID_ARGUMENT: no input
+ *     channels, group_by_count outside 1 .. 8, aggregate_count outside 0 .. 16, a channel out of range, an unknown type, fn, step or
+ *     output_mem, a mask that is not BOOLEAN, an input_type that differs from the channel's type, sum / avg over VARCHAR, BOOLEAN, DATE
+ *     or PA_ROW.  PA_ERR_NOT_SUPPORTED: step PARTIAL or FINAL, more than 64 input channels, PA_LONG_DECIMAL / PA_ROW group channels,
+ *     sum / avg over PA_DECIMAL / PA_LONG_DECIMAL, min / max over VARCHAR, PA_LONG_DECIMAL or PA_ROW, count over PA_ROW.
+ *   Where this differs from the reference (rows and their order are the reference's): the group columns always carry the bits of the
+ *     run's first row (the reference takes them from whichever page flushes the run, so for runs that mix -0.0 / +0.0 or NaN payloads
+ *     they depend on the page cuts); output pages are cut per input page, not by PageBuilder.isFull. */
+typedef struct pa_streaming_aggregation_desc {   /* StreamingAggregationOperator.createOperatorFactory(sourceTypes, groupByTypes, groupByChannels, aggregatorFactories) */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere; NULL = all 0 */
+    int32_t group_by_count;              /* 1 .. 8 */
+    const int32_t* group_by_channels;
+    int32_t step;                        /* pa_agg_step: PA_STEP_SINGLE */
+    int32_t aggregate_count;             /* 0 .. 16 */
+    const pa_aggregate* aggregates;      /* mask_channel included */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_streaming_aggregation_desc;
+
+/* AssignUniqueIdOperator: the first operator of every decorrelated scalar subquery / EXISTS (AssignUniqueId -> LookupJoin probe outer ->
+ * an aggregation grouped by the id), planned by LocalExecutionPlanner.visitAssignUniqueId (AssignUniqueIdOperator.java:115-162).
+ * The output page is the input page with one BIGINT column appended (Page.appendColumn); it never has nulls.  Row i of the operator's
+ * life gets
+ *     (stage_id << 54) | (task_id << 40) | row_id
+ * where row ids come out of a pool -- the factory's AtomicLong, shared by the operators of one factory; pa_unique_id_pool below -- in
+ * blocks of 2^20 (getAndAdd), each block capped at 2^40.  The first block is taken at creation, the next when a row finds the current
+ * one used up, in the middle of a page where that is where it ends: an operator's ids ascend, and no two operators of one pool ever
+ * give out the same id.  A block that would start at or beyond 2^40 fails the call that asked for it -- creation or pa_op_add_input
+ * -- with PA_ERR_ILLEGAL_STATE ("Unique row id exceeds a limit"); the pool has moved on by then, as the reference's has, and the
+ * operator can still be closed and destroyed.
+ *   One output page per non-empty input page; needs_input is 0 while a page is pending; is_finished = finishing and nothing pending.
+ *   Empty input pages are accepted and produce nothing.  A PA_MEM_DEVICE input page given to a PA_MEM_DEVICE operator comes out with
+ *   its own blocks and encodings (zero copy) and the new column behind them; a PA_PAGE_RETAINED page is released once its output page
+ *   has been let go.
+ *   Checks at creation, before the device is asked for, an invalid argument before a refusal: PA_ERR_INVALID_ARGUMENT for no input
+ *   channels, an unknown input type or output_mem, a stage_id outside 0 .. 2^9 - 1 or a task_id outside 0 .. 2^23 - 1 (their shifted
+ *   bits would leave int64 or reach into the row id's 40 bits); PA_ERR_NOT_SUPPORTED for PA_ROW channels and more than 64 channels. */
+typedef struct pa_assign_unique_id_desc {   /* AssignUniqueIdOperator.createOperatorFactory; TaskId of the ProcessorContext */
+    int32_t input_channel_count;
+    const int32_t* input_types;
+    const int32_t* input_type_params;    /* as elsewhere; NULL = all 0 */
+    int32_t stage_id;                    /* taskId.getStageId().getId() */
+    int32_t task_id;                     /* taskId.getId() (the partition id) */
+    int32_t output_mem;                  /* pa_mem */
+    void* stream;
+} pa_assign_unique_id_desc;
+
 /* RowNumberOperator: `row_number() OVER (PARTITION BY k)` and, with max_rows_per_partition, `... WHERE rn <= m` / "any m rows per key",
  * planned by LocalExecutionPlanner.visitRowNumber (:900-938) (RowNumberOperator.java: state machine :183-209, getRowsWithRowNumber
  * :289-299, getSelectedRows :313-342), over GroupByHash.getGroupIds like the two operators above.  The partition of a row is its group
@@ -1033,6 +1105,16 @@ int32_t pa_topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* cap
 int32_t pa_window_create(const pa_window_desc* desc, pa_operator** out);
 /* Window with frames: the ranking functions and count / sum / min / max (pa_framed_window_desc above). */
 int32_t pa_framed_window_create(const pa_framed_window_desc* desc, pa_operator** out);
+/* StreamingAggregation (pa_streaming_aggregation_desc above). */
+int32_t pa_streaming_aggregation_create(const pa_streaming_aggregation_desc* desc, pa_operator** out);
+/* AssignUniqueId (pa_assign_unique_id_desc above).  The pool is the factory's AtomicLong: one per factory, handed to every operator
+ * the factory creates; it is thread safe, and it and its operators may be destroyed in any order.  first_value (0 .. 2^40; anything
+ * else is PA_ERR_INVALID_ARGUMENT) is where the row ids start: the reference starts at 0, another value lets a caller reach the end
+ * of a block or the limit without 2^40 rows. */
+typedef struct pa_unique_id_pool pa_unique_id_pool;
+int32_t pa_unique_id_pool_create(int64_t first_value, pa_unique_id_pool** out);
+int32_t pa_unique_id_pool_destroy(pa_unique_id_pool* pool);
+int32_t pa_assign_unique_id_create(const pa_assign_unique_id_desc* desc, pa_unique_id_pool* pool, pa_operator** out);
 
 /* ---- Operator protocol (Operator.java:21-103; call order Driver.java:355-457) ---- */
 int32_t pa_op_needs_input(pa_operator* op);                 /* 1 / 0 */

@@ -590,6 +590,69 @@ inline std::unique_ptr<Operator> createDistinctLimitOperator(const std::vector<i
     return std::make_unique<Operator>(h);
 }
 
+// StreamingAggregationOperator.createOperatorFactory(sourceTypes, groupByTypes, groupByChannels, step, aggregatorFactories): one output row
+// per run of consecutive rows that are not distinct on the group channels, in input order
+inline std::unique_ptr<Operator> createStreamingAggregationOperator(const std::vector<int32_t>& inputTypes, const std::vector<int32_t>& groupByChannels,
+                                                                    const std::vector<pa_aggregate>& aggregates, int32_t step = PA_STEP_SINGLE,
+                                                                    int32_t outputMem = PA_MEM_HOST, const std::vector<int32_t>& typeParams = {})
+{
+    pa_streaming_aggregation_desc d{};
+    d.input_channel_count = (int32_t)inputTypes.size();
+    d.input_types = inputTypes.data();
+    d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+    d.group_by_count = (int32_t)groupByChannels.size();
+    d.group_by_channels = groupByChannels.data();
+    d.step = step;
+    d.aggregate_count = (int32_t)aggregates.size();
+    d.aggregates = aggregates.data();
+    d.output_mem = outputMem;
+    pa_operator* h = nullptr;
+    check(pa_streaming_aggregation_create(&d, &h));
+    return std::make_unique<Operator>(h);
+}
+
+// The AtomicLong valuePool of AssignUniqueIdOperator's factory: row ids in blocks of 2^20 (firstValue: where they start, 0 in the reference)
+class UniqueIdPool {
+public:
+    explicit UniqueIdPool(int64_t firstValue = 0) { check(pa_unique_id_pool_create(firstValue, &h_)); }
+    ~UniqueIdPool() { pa_unique_id_pool_destroy(h_); }
+    UniqueIdPool(const UniqueIdPool&) = delete;
+    UniqueIdPool& operator=(const UniqueIdPool&) = delete;
+    pa_unique_id_pool* handle() const { return h_; }
+
+private:
+    pa_unique_id_pool* h_ = nullptr;
+};
+
+// AssignUniqueIdOperator.createOperatorFactory: the input page with a BIGINT column appended, (stageId << 54) | (taskId << 40) | row id.
+// The factory owns the pool its operators share; stageId / taskId are the TaskId's.
+class AssignUniqueIdOperatorFactory {
+public:
+    explicit AssignUniqueIdOperatorFactory(std::vector<int32_t> inputTypes, int32_t stageId = 0, int32_t taskId = 0, int32_t outputMem = PA_MEM_HOST,
+                                           std::vector<int32_t> typeParams = {}, int64_t firstValue = 0)
+        : inputTypes(std::move(inputTypes)), typeParams(std::move(typeParams)), stageId(stageId), taskId(taskId), outputMem(outputMem), pool(firstValue)
+    {
+    }
+    std::unique_ptr<Operator> createOperator() const
+    {
+        pa_assign_unique_id_desc d{};
+        d.input_channel_count = (int32_t)inputTypes.size();
+        d.input_types = inputTypes.data();
+        d.input_type_params = typeParams.empty() ? nullptr : typeParams.data();
+        d.stage_id = stageId;
+        d.task_id = taskId;
+        d.output_mem = outputMem;
+        pa_operator* h = nullptr;
+        check(pa_assign_unique_id_create(&d, pool.handle(), &h));
+        return std::make_unique<Operator>(h);
+    }
+
+private:
+    std::vector<int32_t> inputTypes, typeParams;
+    int32_t stageId, taskId, outputMem;
+    UniqueIdPool pool;
+};
+
 // keys seen so far (nextDistinctId) of a MarkDistinct / DistinctLimit operator
 inline int64_t distinctCount(Operator& op)
 {

@@ -87,6 +87,15 @@ final class GpuNative
     static native long createDistinctLimit(int[] inputTypes, int[] typeParams, int[] distinctChannels, long limit, int hashChannel, int expectedDistinct, int outputMem);
     /** {distinct keys seen so far, slots of the table} of a MarkDistinct / DistinctLimit operator (GroupByHash.getGroupCount / getCapacity). */
     static native long[] distinctStats(long operator);
+    /** StreamingAggregationOperator.createOperatorFactory(sourceTypes, groupByTypes, groupByChannels, step, aggregatorFactories): one row per
+     *  run of consecutive rows with one group key; the aggregates as for createHashAggregation (GpuStreamingAggregation). */
+    static native long createStreamingAggregation(int[] inputTypes, int[] typeParams, int[] groupByChannels, int step, int[] aggFns, int[] aggInputs,
+            int[] aggMasks, int[] aggInputTypes, int outputMem);
+    /** The AtomicLong valuePool of AssignUniqueIdOperator's factory: row ids in blocks of 2^20, starting at firstValue (GpuAssignUniqueId). */
+    static native long createUniqueIdPool(long firstValue);
+    static native void destroyUniqueIdPool(long uniqueIdPool);
+    /** AssignUniqueIdOperator: the input page plus a BIGINT id, (stageId << 54) | (taskId << 40) | row id; typeParams may be null. */
+    static native long createAssignUniqueId(long uniqueIdPool, int[] inputTypes, int[] typeParams, int stageId, int taskId, int outputMem);
     /** RowNumberOperatorFactory(sourceTypes, outputChannels, partitionChannels, partitionTypes, maxRowsPerPartition, hashChannel, expectedPositions);
      *  maxRowsPerPartition = -1: absent (GpuRowNumber). */
     static native long createRowNumber(int[] inputTypes, int[] typeParams, int[] outputChannels, int[] partitionChannels, long maxRowsPerPartition,

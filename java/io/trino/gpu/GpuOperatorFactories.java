@@ -114,6 +114,26 @@ public final class GpuOperatorFactories
         return GpuNestedLoopJoin.create(buildOperatorId, buildNodeId, buildTypes, joinOperatorId, joinNodeId, probeTypes, probeChannels, buildChannels, filterAbove);
     }
 
+    /**
+     * An AssignUniqueId node (LocalExecutionPlanner.visitAssignUniqueId: `AssignUniqueIdOperator.createOperatorFactory(...)`), the first
+     * operator of a decorrelated scalar subquery: not a method of OperatorFactories either.  Optional.empty(): keep the reference factory.
+     */
+    public static Optional<OperatorFactory> assignUniqueId(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes)
+    {
+        return GpuAssignUniqueId.create(operatorId, planNodeId, sourceTypes);
+    }
+
+    /**
+     * An AggregationNode whose input arrives grouped by all its keys (LocalExecutionPlanner.visitAggregation's streamable branch:
+     * `StreamingAggregationOperator.createOperatorFactory(...)`) with step SINGLE -- behind AssignUniqueId and a probe-outer join, the
+     * aggregation of a decorrelated scalar subquery.  Optional.empty(): keep the reference factory.
+     */
+    public static Optional<OperatorFactory> streamingAggregation(int operatorId, PlanNodeId planNodeId, List<Type> sourceTypes, List<Integer> groupByChannels,
+            int step, int[] aggFns, int[] aggInputs, int[] aggMasks, List<Type> outputTypes)
+    {
+        return GpuStreamingAggregation.create(operatorId, planNodeId, sourceTypes, groupByChannels, step, aggFns, aggInputs, aggMasks, outputTypes);
+    }
+
     private static OperatorFactory lookupJoin(int operatorId, PlanNodeId planNodeId, long bridge, int joinType, boolean outputSingleMatch, List<Type> probeTypes,
             List<Integer> probeJoinChannel, OptionalInt probeHashChannel, Optional<List<Integer>> probeOutputChannels, long filterExpression)
     {

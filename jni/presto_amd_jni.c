@@ -640,7 +640,57 @@ JNIEXPORT jlongArray JNICALL Java_io_trino_gpu_GpuNative_distinctStats(JNIEnv* e
     return out;
 }
 
-/* LocalExecutionPlanner.visitRowNumber: RowNumberOperatorFactory.  maxRowsPerPartition = -1: absent; typeParams as above. */
+/* LocalExecutionPlanner.visitAggregation, the streamable branch with step SINGLE: StreamingAggregationOperator.createOperatorFactory.  The
+ * aggregates as for createHashAggregation; typeParams as above. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createStreamingAggregation(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,
+        jintArray groupByChannels, jint step, jintArray aggFns, jintArray aggInputs, jintArray aggMasks, jintArray aggInputTypes, jint outputMem)
+{
+    jsize n, ng, na, np_ = 0;
+    pa_streaming_aggregation_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t *types = ints_of(env, inputTypes, &n), *gb = ints_of(env, groupByChannels, &ng);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    pa_aggregate* aggs;
+    fill_aggregates(env, aggFns, aggInputs, aggMasks, aggInputTypes, &aggs, &na);
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.group_by_count = ng; d.group_by_channels = gb; d.step = step;
+    d.aggregate_count = na; d.aggregates = aggs; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_streaming_aggregation_create(&d, &op);
+    free(aggs); free(params); free(gb); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+/* LocalExecutionPlanner.visitAssignUniqueId: AssignUniqueIdOperator.createOperatorFactory. The pool is the factory's AtomicLong (one per
+ * factory, created with 0); stageId / taskId are the TaskId's of the operator's ProcessorContext; typeParams as above. */
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createUniqueIdPool(JNIEnv* env, jclass c, jlong firstValue)
+{
+    pa_unique_id_pool* pool = 0;
+    int32_t rc = pa_unique_id_pool_create(firstValue, &pool);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)pool;
+}
+JNIEXPORT void JNICALL Java_io_trino_gpu_GpuNative_destroyUniqueIdPool(JNIEnv* env, jclass c, jlong h) { CHECK(pa_unique_id_pool_destroy((pa_unique_id_pool*)(intptr_t)h)); }
+
+JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createAssignUniqueId(JNIEnv* env, jclass c, jlong pool, jintArray inputTypes, jintArray typeParams,
+        jint stageId, jint taskId, jint outputMem)
+{
+    jsize n, np_ = 0;
+    pa_assign_unique_id_desc d;
+    memset(&d, 0, sizeof d);
+    int32_t* types = ints_of(env, inputTypes, &n);
+    int32_t* params = typeParams ? ints_of(env, typeParams, &np_) : 0;
+    d.input_channel_count = n; d.input_types = types; d.input_type_params = params && np_ == n ? params : 0;
+    d.stage_id = stageId; d.task_id = taskId; d.output_mem = outputMem;
+    pa_operator* op = 0;
+    int32_t rc = pa_assign_unique_id_create(&d, (pa_unique_id_pool*)(intptr_t)pool, &op);
+    free(params); free(types);
+    if (rc < 0) { throw_native(env, rc); return 0; }
+    return (jlong)(intptr_t)op;
+}
+
+/* LocalExecutionPlanner.visitRowNumber: RowNumberOperatorFactory. maxRowsPerPartition = -1: absent; typeParams as above. */
 JNIEXPORT jlong JNICALL Java_io_trino_gpu_GpuNative_createRowNumber(JNIEnv* env, jclass c, jintArray inputTypes, jintArray typeParams,
         jintArray outputChannels, jintArray partitionChannels, jlong maxRowsPerPartition, jint hashChannel, jint expectedPositions, jint outputMem)
 {

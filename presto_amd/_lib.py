@@ -75,6 +75,10 @@ def lib():
     L.pa_topn_ranking_stats.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.pa_window_create.argtypes = [C.POINTER(abi.pa_window_desc), C.POINTER(vp)]
     L.pa_framed_window_create.argtypes = [C.POINTER(abi.pa_framed_window_desc), C.POINTER(vp)]
+    L.pa_streaming_aggregation_create.argtypes = [C.POINTER(abi.pa_streaming_aggregation_desc), C.POINTER(vp)]
+    L.pa_unique_id_pool_create.argtypes = [C.c_int64, C.POINTER(vp)]
+    L.pa_unique_id_pool_destroy.argtypes = [vp]
+    L.pa_assign_unique_id_create.argtypes = [C.POINTER(abi.pa_assign_unique_id_desc), vp, C.POINTER(vp)]
     L.pa_fused_join_aggregation_create.argtypes = [C.POINTER(abi.pa_fused_join_aggregation_desc), vp, C.POINTER(vp)]
     L.pa_fused_join_create.argtypes = [C.POINTER(abi.pa_fused_join_desc), vp, C.POINTER(vp)]
     L.pa_codegen_fused_join.argtypes = [C.POINTER(abi.pa_fused_join_aggregation_desc), C.POINTER(abi.pa_hash_builder_desc), C.c_int32, C.c_char_p, C.c_int64]

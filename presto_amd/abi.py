@@ -378,6 +378,33 @@ class pa_distinct_limit_desc(C.Structure):
     ]
 
 
+class pa_streaming_aggregation_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("group_by_count", C.c_int32),
+        ("group_by_channels", C.POINTER(C.c_int32)),
+        ("step", C.c_int32),
+        ("aggregate_count", C.c_int32),
+        ("aggregates", C.POINTER(pa_aggregate)),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class pa_assign_unique_id_desc(C.Structure):
+    _fields_ = [
+        ("input_channel_count", C.c_int32),
+        ("input_types", C.POINTER(C.c_int32)),
+        ("input_type_params", C.POINTER(C.c_int32)),
+        ("stage_id", C.c_int32),
+        ("task_id", C.c_int32),
+        ("output_mem", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
 class pa_row_number_desc(C.Structure):
     _fields_ = [
         ("input_channel_count", C.c_int32),

@@ -736,6 +736,41 @@ int32_t pa_framed_window_create(const pa_framed_window_desc* desc, pa_operator**
     });
 }
 
+// ---- StreamingAggregation ----
+int32_t pa_streaming_aggregation_create(const pa_streaming_aggregation_desc* desc, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_streaming_aggregation(desc);
+        return PA_OK;
+    });
+}
+
+// ---- AssignUniqueId ----
+int32_t pa_unique_id_pool_create(int64_t first_value, pa_unique_id_pool** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "out is null");
+        *out = unique_id_pool_new(first_value);
+        return PA_OK;
+    });
+}
+int32_t pa_unique_id_pool_destroy(pa_unique_id_pool* pool)
+{
+    return guarded([&]() -> int32_t {
+        if (pool) unique_id_pool_delete(pool);
+        return PA_OK;
+    });
+}
+int32_t pa_assign_unique_id_create(const pa_assign_unique_id_desc* desc, pa_unique_id_pool* pool, pa_operator** out)
+{
+    return guarded([&]() -> int32_t {
+        PA_REQUIRE(out != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+        *out = make_assign_unique_id(desc, pool);
+        return PA_OK;
+    });
+}
+
 // ---- partitioned exchange ----
 int32_t pa_comm_unique_id(void* id_out)
 {

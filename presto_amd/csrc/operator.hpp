@@ -89,6 +89,12 @@ void topn_ranking_stats(pa_operator* op, int64_t* partitions, int64_t* capacity,
 pa_operator* make_window(const pa_window_desc* desc);
 // the same operator from the framed descriptor: the ranking functions and count / sum / min / max
 pa_operator* make_framed_window(const pa_framed_window_desc* desc);
+// StreamingAggregationOperator (op_streaming_agg.cpp)
+pa_operator* make_streaming_aggregation(const pa_streaming_aggregation_desc* desc);
+// AssignUniqueIdOperator and the row-id pool of its factory (op_assign_unique_id.cpp)
+pa_unique_id_pool* unique_id_pool_new(int64_t first_value);
+void unique_id_pool_delete(pa_unique_id_pool* pool);
+pa_operator* make_assign_unique_id(const pa_assign_unique_id_desc* desc, pa_unique_id_pool* pool);
 // the consumer of an aggregation's output is a TopN over it: groups that cannot be among its n best rows may be left out (op_fused.cpp, op_fused_output.cpp);
 // false: the operator does not take the hint (it emits everything)
 bool aggregation_set_output_topn(pa_operator* op, int64_t n, const int32_t* sort_channels, const int32_t* sort_orders, int32_t count);

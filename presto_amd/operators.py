@@ -955,6 +955,105 @@ def DistinctLimitOperator(input_types, distinct_channels, limit, hash_channel=-1
                                         type_params).createOperator()
 
 
+# ---- STREAMING AGGREGATION ---------------------------------------------------------------------------------
+def streaming_aggregation_desc(input_types, group_by_channels, aggregates, step=abi.STEP_SINGLE, output_mem=abi.MEM_HOST, stream=None,
+                               type_params=None):
+    """aggregates: (fn, input channel, input type[, mask channel]) as for HashAggregationOperator"""
+    d = abi.pa_streaming_aggregation_desc()
+    types = abi.int32_array(input_types)
+    gb = abi.int32_array(group_by_channels)
+    aggs = _aggregates(aggregates)
+    keep = [types, gb, aggs]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.group_by_count = len(group_by_channels)
+    d.group_by_channels = C.cast(gb, C.POINTER(C.c_int32))
+    d.step = step
+    d.aggregate_count = len(aggregates)
+    d.aggregates = C.cast(aggs, C.POINTER(abi.pa_aggregate))
+    d.output_mem = output_mem
+    d.stream = stream
+    return d, keep
+
+
+def StreamingAggregationOperatorFactory(input_types, group_by_channels, aggregates, step=abi.STEP_SINGLE, output_mem=abi.MEM_HOST, stream=None,
+                                        type_params=None):
+    """StreamingAggregationOperator.createOperatorFactory (…/operator/StreamingAggregationOperator.java): one output row per run of
+    consecutive rows with one group key, in input order -- the aggregation over input that arrives grouped."""
+    d, keep = streaming_aggregation_desc(input_types, group_by_channels, aggregates, step, output_mem, stream, type_params)
+    return OperatorFactory(lib().pa_streaming_aggregation_create, d, keep)
+
+
+def StreamingAggregationOperator(input_types, group_by_channels, aggregates, step=abi.STEP_SINGLE, output_mem=abi.MEM_HOST, stream=None,
+                                 type_params=None):
+    return StreamingAggregationOperatorFactory(input_types, group_by_channels, aggregates, step, output_mem, stream, type_params).createOperator()
+
+
+# ---- ASSIGN UNIQUE ID --------------------------------------------------------------------------------------
+class UniqueIdPool:
+    """The AtomicLong valuePool of AssignUniqueIdOperator's factory (…/operator/AssignUniqueIdOperator.java:53): row ids are taken from
+    it in blocks of 2^20.  `first_value` other than 0 is for reaching block ends and the 2^40 limit without that many rows."""
+
+    def __init__(self, first_value=0):
+        h = C.c_void_p()
+        check(lib().pa_unique_id_pool_create(first_value, C.byref(h)))
+        self._h = h
+
+    def destroy(self):
+        if self._h:
+            lib().pa_unique_id_pool_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def assign_unique_id_desc(input_types, stage_id=0, task_id=0, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    d = abi.pa_assign_unique_id_desc()
+    types = abi.int32_array(input_types)
+    keep = [types]
+    d.input_channel_count = len(input_types)
+    d.input_types = C.cast(types, C.POINTER(C.c_int32))
+    type_params = _params_of(input_types, type_params)
+    if type_params is not None:
+        tp = abi.int32_array(type_params)
+        keep.append(tp)
+        d.input_type_params = C.cast(tp, C.POINTER(C.c_int32))
+    d.stage_id = stage_id
+    d.task_id = task_id
+    d.output_mem = output_mem
+    d.stream = stream
+    return d, keep
+
+
+class AssignUniqueIdOperatorFactory(OperatorFactory):
+    """AssignUniqueIdOperator.createOperatorFactory (…/operator/AssignUniqueIdOperator.java:42-97): the factory owns the pool its
+    operators draw from (`pool`: share one between factories that stand for one plan node); stage_id / task_id are the TaskId's."""
+
+    def __init__(self, input_types, stage_id=0, task_id=0, pool=None, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+        d, keep = assign_unique_id_desc(input_types, stage_id, task_id, output_mem, stream, type_params)
+        super().__init__(lib().pa_assign_unique_id_create, d, keep)
+        self.pool = pool if pool is not None else UniqueIdPool()
+
+    def createOperator(self):
+        h = C.c_void_p()
+        check(self._create(C.byref(self._desc), self.pool._h, C.byref(h)))
+        return Operator(h, [self._keep, self.pool])
+
+
+def AssignUniqueIdOperator(input_types, stage_id=0, task_id=0, pool=None, output_mem=abi.MEM_HOST, stream=None, type_params=None):
+    """The input page with one BIGINT column appended: (stage_id << 54) | (task_id << 40) | row id."""
+    return AssignUniqueIdOperatorFactory(input_types, stage_id, task_id, pool, output_mem, stream, type_params).createOperator()
+
+
 # ---- ROW_NUMBER --------------------------------------------------------------------------------------------
 def RowNumberOperatorFactory(input_types, output_channels, partition_channels, max_rows_per_partition=None, hash_channel=-1, expected_positions=0,
                              output_mem=abi.MEM_HOST, stream=None, type_params=None):
