@@ -1284,7 +1284,9 @@ int32_t pa_page_buffer_free(pa_page_buffer* buffer);
 /* Block.copyPositions for a VariableWidthBlock, in two calls (the byte total sizes the second one's output):
  * pa_varwidth_gather_offsets: out_lengths[i] = length of row positions[i]; out_offsets[count + 1] = their exclusive scan
  * (out_offsets[count] = total); *total_bytes_host = total.  pa_varwidth_gather_bytes copies the bytes behind those offsets.
- * pa_offsets_from_lengths: exclusive scan of per-row lengths into count + 1 offsets (what a receiver of shuffled rows does). */
+ * pa_offsets_from_lengths: exclusive scan of per-row lengths into count + 1 offsets (what a receiver of shuffled rows does).
+ * Both add the total in 64 bits: *total_bytes_host is the true total also when it is 2^31 or more, which one block's 32-bit offsets
+ * cannot hold -- the call then fails with PA_ERR_INSUFFICIENT_RESOURCES, and the offsets written are not to be used. */
 int32_t pa_varwidth_gather_offsets(const int32_t* offsets, const int32_t* positions, int32_t count, int32_t* out_lengths,
                                    int32_t* out_offsets, int64_t* total_bytes_host, void* stream);
 int32_t pa_varwidth_gather_bytes(const void* values, const int32_t* offsets, const int32_t* positions, int32_t count,

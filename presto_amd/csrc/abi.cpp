@@ -10,6 +10,7 @@
 #include "exprgen.hpp"
 #include "jit.hpp"
 #include "operator.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 #include "static_kernels.hpp"
 
@@ -1130,23 +1131,23 @@ int32_t pa_gather_flat(const void* src, int32_t elem_bytes, const int32_t* posit
 }
 
 namespace {
-// exclusive scan of n lengths already sitting in offs[0..n) into offs[0..n], total to the host
-int64_t scan_lengths_in_place(int32_t* offs, int32_t n, hipStream_t s)
+// exclusive scan of n lengths already sitting in offs[0..n) into offs[0..n]; the byte total, added in 64 bits, to *total_host.  2^31 bytes
+// and more do not fit the 32-bit offsets: *total_host still holds the true total, and the call fails with INSUFFICIENT_RESOURCES
+// (the offsets written are then meaningless, and the caller must not size or fill a buffer by them).
+void scan_lengths_in_place(int32_t* offs, int32_t n, int64_t* total_host, hipStream_t s)
 {
+    *total_host = 0;
+    if (n == 0) {
+        PA_HIP(hipMemsetAsync(offs, 0, 4, s));
+        PA_HIP(hipStreamSynchronize(s));
+        return;
+    }
     pa::DevBuf temp, total;
     int32_t* t = static_cast<int32_t*>(total.ensure(64));
-    PA_HIP(hipMemsetAsync(t, 0, 4, s));
-    int32_t h = 0;
-    if (n > 0) {
-        pa::launch_exclusive_scan_i32(offs, offs, n, t, temp.ensure(pa::scan_temp_bytes(n)), s);
-        PA_HIP(hipMemcpyAsync(offs + n, t, 4, hipMemcpyDeviceToDevice, s));
-        PA_HIP(hipMemcpyAsync(&h, t, 4, hipMemcpyDeviceToHost, s));
-    }
-    else {
-        PA_HIP(hipMemsetAsync(offs, 0, 4, s));
-    }
+    pa::checked_varwidth_offsets(offs, n, t, temp.ensure(pa::scan_temp_bytes(n)), s,
+                                 "the VARCHAR rows hold more than 2 GiB of bytes: they do not fit one block's 32-bit offsets", total_host);
+    PA_HIP(hipMemcpyAsync(offs + n, t, 4, hipMemcpyDeviceToDevice, s));
     PA_HIP(hipStreamSynchronize(s));  // temp / total go back to the pool
-    return h;
 }
 }  // namespace
 
@@ -1161,7 +1162,7 @@ int32_t pa_varwidth_gather_offsets(const int32_t* offsets, const int32_t* positi
             launch_varwidth_lengths(positions, count, offsets, nullptr, out_offsets, s);
             if (out_lengths) PA_HIP(hipMemcpyAsync(out_lengths, out_offsets, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
         }
-        *total_bytes_host = scan_lengths_in_place(out_offsets, count, s);
+        scan_lengths_in_place(out_offsets, count, total_bytes_host, s);
         return PA_OK;
     });
 }
@@ -1189,7 +1190,7 @@ int32_t pa_offsets_from_lengths(const int32_t* lengths, int32_t count, int32_t* 
         require_device();
         hipStream_t s = (hipStream_t)stream;
         if (count > 0) PA_HIP(hipMemcpyAsync(out_offsets, lengths, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-        *total_bytes_host = scan_lengths_in_place(out_offsets, count, s);
+        scan_lengths_in_place(out_offsets, count, total_bytes_host, s);
         return PA_OK;
     });
 }

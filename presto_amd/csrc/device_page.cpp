@@ -1,5 +1,6 @@
 // device_page.cpp -- see device_page.hpp.
 #include "device_page.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 
 namespace pa {
@@ -279,12 +280,14 @@ DevPage PageStager::stage(const pa_page* page, const std::vector<bool>* needed, 
                 int32_t* total = static_cast<int32_t*>(arena(slot + 6, 64));
                 PA_HIP(hipMemsetAsync(out_off, 0, (rows + 1) * 4, stream));
                 PA_HIP(hipMemsetAsync(total, 0, 4, stream));
-                int32_t h_total = 0;
+                // The decoded bytes multiply (n positions of a dictionary entry): the reference never materialises such a block, so a
+                // legal page may decode to 2 GiB and more.  The total is added in 64 bits and refused here, before the byte arena is
+                // sized by it and before the copy: every operator's "one staged block holds under 2 GiB" rests on this check.
+                int64_t h_total = 0;
                 if (n > 0) {
                     launch_varwidth_lengths(ids, n, doff, dnulls, out_off, stream);
-                    launch_exclusive_scan_i32(out_off, out_off, n, total, arena(slot + 7, scan_temp_bytes(n)), stream);
-                    PA_HIP(hipMemcpyAsync(&h_total, total, 4, hipMemcpyDeviceToHost, stream));
-                    PA_HIP(hipStreamSynchronize(stream));
+                    h_total = checked_varwidth_offsets(out_off, n, total, arena(slot + 7, scan_temp_bytes(n)), stream,
+                                                       "a dictionary / RLE VARCHAR block decodes to more than 2 GiB of bytes");
                 }
                 uint8_t* out_bytes = static_cast<uint8_t*>(arena(slot + 5, (size_t)(h_total > 0 ? h_total : 1)));
                 if (n > 0) launch_varwidth_copy(ids, n, doff, static_cast<const uint8_t*>(dvals), dnulls, out_off, out_bytes, total, stream);

@@ -71,6 +71,7 @@ struct HeldRows {
             const DevColumn& src = in.cols[c];
             OutColumn& h = cols[c];
             if (h.varwidth) {
+                // (no 2 GiB message: a subset of the rows of ONE staged block, which holds under 2 GiB -- PageStager::stage; the sum with the rows held is checked in append_offsets)
                 const int32_t add = gather.copy_positions(src, positions, k, varchar_tmp, s);   // offsets from 0, k + 1 of them
                 char* v = append_offsets(c, varchar_tmp.offsets.as<int32_t>(), k, add, s);
                 if (add) PA_HIP(hipMemcpyAsync(v, varchar_tmp.values.ptr(), (size_t)add, hipMemcpyDeviceToDevice, s));
@@ -91,6 +92,7 @@ struct HeldRows {
         for (size_t c = 0; c < cols.size(); c++) {
             if (!held[c]) continue;
             OutColumn fresh;
+            // (no 2 GiB message: the callers keep each held row at most once, and the held column is at most INT32_MAX bytes -- append_offsets)
             var_bytes[c] = gather.copy_positions(view((int32_t)c), rowids, kept, fresh, s);
             cols[c] = std::move(fresh);   // (the old arrays go back to the pool tagged with this stream)
         }
@@ -135,6 +137,7 @@ struct HeldRows {
             GatherMultiCol& gc = gm.col[gm.ncols];
             memset(&gc, 0, sizeof gc);
             gc.width = 1;
+            // (no 2 GiB message: perm is a permutation of, or distinct rows among, the rows held -- at most INT32_MAX bytes, append_offsets)
             if (h.varwidth) gather.copy_varwidth(h, perm, (int32_t)n, oc.offsets, oc.values, s);
             else {
                 const int w = type_width(h.type);   // (1, 4, 8, or 16 for a LONG_DECIMAL: creation refused every other type)

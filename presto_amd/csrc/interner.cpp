@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "intern_kernels.hpp"
+#include "position_gather.hpp"
 #include "scan_kernels.hpp"
 
 namespace pa {
@@ -110,14 +111,10 @@ void StringInterner::decode(const int32_t* ids, const uint8_t* nulls, int64_t n,
     launch_intern_lengths(view(), ids, nulls, n, offs, s);
     DevBuf temp, total;
     int32_t* t = static_cast<int32_t*>(total.ensure(64));
-    launch_exclusive_scan_i32(offs, offs, n, t, temp.ensure(scan_temp_bytes(n)), s);
+    // (the total in 64 bits, refused before the byte buffer is sized by it: ids repeat, so the column may exceed the arena many times)
+    const int64_t bytes = checked_varwidth_offsets(offs, n, t, temp.ensure(scan_temp_bytes(n)), s, "VARCHAR key column exceeds 2 GiB");
     PA_HIP(hipMemcpyAsync(offs + n, t, 4, hipMemcpyDeviceToDevice, s));
-    int32_t* h = static_cast<int32_t*>(h_.ensure(64));
-    PA_HIP(hipMemcpyAsync(h + 8, t, 4, hipMemcpyDeviceToHost, s));
-    PA_HIP(hipStreamSynchronize(s));
-    const int32_t bytes = h[8];
-    PA_REQUIRE(bytes >= 0, PA_ERR_INSUFFICIENT_RESOURCES, "VARCHAR key column exceeds 2 GiB");
-    uint8_t* out = static_cast<uint8_t*>(values->ensure((size_t)std::max(bytes, 1)));
+    uint8_t* out = static_cast<uint8_t*>(values->ensure((size_t)std::max<int64_t>(bytes, 1)));
     launch_intern_bytes(view(), ids, nulls, n, offs, out, s);
 }
 

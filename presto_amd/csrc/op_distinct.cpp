@@ -176,6 +176,7 @@ public:
         if (k == 0) return;
         remaining_ -= k;
         out_cols_.resize(output_channels_.size());
+        // (no 2 GiB message: the first rows of their keys, each once, of ONE staged block -- under 2 GiB, PageStager::stage)
         for (size_t c = 0; c < output_channels_.size(); c++) gather_.copy_positions(in.cols[output_channels_[c]], positions, (int32_t)k, out_cols_[c], s);
         n_ = (int32_t)k;
         pending_ = true;

@@ -196,6 +196,8 @@ public:
                 PA_HIP(hipMemcpyAsync(hb + d, v.offsets->as<int32_t>() + first[d], 4, hipMemcpyDeviceToHost, s));
             }
             PA_HIP(hipStreamSynchronize(s));
+            // (a sign check of the 32-bit total is enough HERE: the lengths are those of a permutation of one staged block's rows, and
+            // PageStager::stage refuses a block that decodes to 2^31 bytes and more, so the true total is under 2^31 and cannot wrap)
             PA_REQUIRE(hb[W] >= 0, PA_ERR_INSUFFICIENT_RESOURCES, "more than 2 GiB of VARCHAR bytes in one exchange page");
             v.first_byte.assign(hb, hb + W + 1);
             v.bytes = temp((size_t)std::max<int64_t>(hb[W], 1));
@@ -395,9 +397,17 @@ private:
                                  d_table_.ensure(copy_segments_table_bytes(segs.size())), s);
         }
         // ---- the all-to-all ----
-        hipEvent_t e0, e1;
-        PA_HIP(hipEventCreate(&e0));
-        PA_HIP(hipEventCreate(&e1));
+        struct Events {   // (destroyed on every way out: the refusal below throws between their creation and their last use)
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            ~Events()
+            {
+                if (e0) (void)hipEventDestroy(e0);
+                if (e1) (void)hipEventDestroy(e1);
+            }
+        } events;
+        PA_HIP(hipEventCreate(&events.e0));
+        PA_HIP(hipEventCreate(&events.e1));
+        const hipEvent_t e0 = events.e0, e1 = events.e1;
         PA_HIP(hipEventRecord(e0, s));
         comm_all_to_all_v(comm, sb, soff.data(), sbytes.data(), rb, roff.data(), rbytes.data(), s);
         PA_HIP(hipEventRecord(e1, s));
@@ -490,8 +500,6 @@ private:
         PA_HIP(hipStreamSynchronize(s));
         float ms = 0;
         PA_HIP(hipEventElapsedTime(&ms, e0, e1));
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         ex_->transfer_ms += ms;
         ex_->rows_received += total_rows;
         for (int p = 0; p < W; p++) {

@@ -644,6 +644,7 @@ public:
             }
             if (oc.varwidth) {
                 // Block.copyPositions for a VariableWidthBlock, out under the type the projection declares
+                // (no 2 GiB message: the selected rows, each once, of ONE staged block -- under 2 GiB, PageStager::stage)
                 gather_.copy_positions(in_.cols[e.node(e.root).channel], positions_.as<int32_t>(), count, oc, s);
                 oc.type = e.root_type();
                 oc.varwidth = true;

@@ -1107,6 +1107,7 @@ public:
                 PA_HIP(hipMemsetAsync(o.values.ensure((size_t)count * type_width(t)), 0, (size_t)count * type_width(t), s));
             }
         }
+        // (no 2 GiB message: the unvisited build rows, each once, out of a build column of at most INT32_MAX bytes -- HashBuilder::add_input)
         for (int c : ls_->output_channels) gather_.copy_positions(ls_->cols[c].view(), pos, count, out_cols_[oc++], s);
         publish_output(out_cols_, count, output_mem_, s, out, out_storage_);
         return true;

@@ -125,6 +125,7 @@ public:
                 positions = p;
             }
             out_cols_.resize(output_channels_.size() + 1);
+            // (no 2 GiB message: the rows kept, each once, of ONE staged block -- under 2 GiB, PageStager::stage)
             for (size_t c = 0; c < output_channels_.size(); c++) gather_.copy_positions(in.cols[output_channels_[c]], positions, kept, out_cols_[c], s);
             OutColumn& o = out_cols_.back();
             o.type = PA_BIGINT;

@@ -134,7 +134,7 @@ public:
 
     void add_input(const pa_page* page) override
     {
-        PA_REQUIRE(!failed_, PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, kOutOfRange);
+        PA_REQUIRE(!failed_, fail_status_, fail_message_);
         PA_REQUIRE(!finishing_ && !pending_, PA_ERR_ILLEGAL_STATE, "Operator does not need input");
         PA_REQUIRE(page != nullptr && page->channel_count == (int32_t)types_.size(), PA_ERR_INVALID_ARGUMENT, "page does not match the input types");
         const int32_t n = page->position_count;
@@ -200,6 +200,7 @@ public:
         }
         // the first row of the run the page leaves open: row start[closed], unless the carried run goes on
         if (!open_ || closed >= 1) {
+            // (no 2 GiB message: ONE row of one staged block -- under 2 GiB, PageStager::stage)
             for (size_t c = 0; c < nk; c++) carry_bytes_[c] = gather_.copy_positions(in.cols[group_channels_[c]], start + closed, 1, carry_key_[c], s);
         }
         open_ = true;
@@ -257,11 +258,17 @@ public:
 private:
     static constexpr const char* kOutOfRange = "bigint addition overflow in sum: a running sum of a group left the range of its type";
 
-    [[noreturn]] void fail()
+    static constexpr const char* kKeyColumnTooLarge =
+        "the group keys of the runs a page closes, the carried run's among them, hold more than 2 GB of VARCHAR bytes in one output column";
+
+    // (the operator is done for: its carry has moved on past rows that no page of output holds)
+    [[noreturn]] void fail(int32_t status = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, const char* message = kOutOfRange)
     {
         failed_ = true;
         pending_ = false;
-        throw Error(PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE, kOutOfRange);
+        fail_status_ = status;
+        fail_message_ = message;
+        throw Error(status, message);
     }
 
     // the arguments of the reduction over page `in` (null: only what the finish launch reads), its output columns sized for n runs
@@ -320,7 +327,7 @@ private:
     {
         OutColumn& o = out_cols_[c];
         if (!open_) {
-            gather_.copy_positions(src, start, k, o, s);
+            gather_.copy_positions(src, start, k, o, s);   // (no 2 GiB message: run start rows, each once, of ONE staged block)
             return;
         }
         const OutColumn& carried = carry_key_[c];
@@ -339,7 +346,10 @@ private:
         }
         const int32_t head = carry_bytes_[c];
         int32_t rest = 0;
+        // (no 2 GiB message for `rest`: run start rows, each once, of ONE staged block -- under 2 GiB, PageStager::stage.  But the column is
+        // that AND the carried key, which came with an earlier block: their sum is checked here, before the buffer is sized by it)
         if (k > 1) rest = gather_.copy_positions(src, start + 1, k - 1, rest_, s);
+        if ((int64_t)head + rest > INT32_MAX) fail(PA_ERR_INSUFFICIENT_RESOURCES, kKeyColumnTooLarge);
         o.type = src.type;
         o.varwidth = true;
         o.has_nulls = true;
@@ -384,6 +394,8 @@ private:
     std::vector<pa_column> storage_;
     int32_t n_ = 0;
     bool pending_ = false, finishing_ = false, failed_ = false;
+    int32_t fail_status_ = PA_ERR_NUMERIC_VALUE_OUT_OF_RANGE;   // what a failed operator answers every later call with
+    const char* fail_message_ = kOutOfRange;
 };
 
 }  // namespace

@@ -326,6 +326,7 @@ private:
             // VARCHAR: copyPositions of the values (the NULL flags went with the side buffer), or the whole block
             std::vector<uint8_t> raw_off, raw_bytes;
             if (positions) {
+                // (no 2 GiB message: the candidate rows, each once, of ONE staged block -- under 2 GiB, PageStager::stage)
                 const int32_t h_total = varchar_gather_.copy_varwidth(col, positions, (int32_t)count, var_off_, var_bytes_, s);
                 fetch(var_off_.ptr(), (size_t)(count + 1) * 4, raw_off);
                 fetch(var_bytes_.ptr(), (size_t)h_total, raw_bytes);

@@ -157,7 +157,9 @@ size_t scan_temp_bytes(int64_t n)
 }
 
 // out[i] = sum(in[0..i)), *total_out = sum(in[0..n)); out may alias in; out has room for n entries.
-// The caller guarantees the sum fits int32 (positions / byte offsets of one Block).
+// The adds are 32-bit and wrap: a sum that fits int32 (positions / byte offsets of one Block) gives the offsets; a larger one leaves
+// meaningless values in out[0..n) and *total_out -- written in bounds all the same -- which the caller must not size or fill a buffer
+// by (checked_varwidth_offsets, position_gather.hpp, adds the same lengths in 64 bits and refuses before anyone does).
 void launch_exclusive_scan_i32(const int32_t* in, int32_t* out, int64_t n, int32_t* total_out, void* temp, hipStream_t s)
 {
     if (n <= 0) {
