@@ -7,25 +7,12 @@
 namespace pa {
 namespace fused {
 
-OwnedExpr input_ref_expr(int32_t channel, int32_t type)
-{
-    OwnedExpr e;
-    pa_expr_node node{};
-    node.kind = PA_EXPR_INPUT_REF;
-    node.type = type;
-    node.channel = channel;
-    e.nodes.push_back(node);
-    e.strings.emplace_back();
-    e.root = 0;
-    return e;
-}
-
 // jd / bridge: the probe stage between the projections and the aggregation (null: none); the aggregation's channels then index
 // the join's output page = [probe output channels, build output channels] (LookupJoinPageBuilder.java:76-139)
 Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc& ag, const pa_lookup_join_desc* jd, pa_lookup_source* bridge)
 {
     Spec s;
-    PA_REQUIRE(fp.input_channel_count > 0 && fp.input_channel_count <= kMaxChannels, PA_ERR_NOT_SUPPORTED,
+    PA_REQUIRE(fp.input_channel_count > 0 && fp.input_channel_count <= PA_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED,
                "fused aggregation supports 1..32 input channels");
     s.n_in = fp.input_channel_count;
     s.in_types.assign(fp.input_types, fp.input_types + s.n_in);
@@ -43,21 +30,14 @@ Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc&
         for (int32_t j = 0; j < fp.projection_count; j++) to_proj.push_back(j);
     }
     else {
-        PA_REQUIRE(bridge != nullptr && bridge->impl != nullptr, PA_ERR_ILLEGAL_STATE, "lookup source has no build operator yet");
         PA_REQUIRE(ag.step == PA_STEP_SINGLE || ag.step == PA_STEP_PARTIAL, PA_ERR_NOT_SUPPORTED, "an aggregation over a join output is SINGLE or PARTIAL");
-        PA_REQUIRE(jd->join_type == PA_JOIN_INNER, PA_ERR_NOT_SUPPORTED, "the fused probe is an inner join");
-        PA_REQUIRE(jd->filter == nullptr, PA_ERR_NOT_SUPPORTED, "a join filter function runs in the LookupJoinOperator, not in the fused probe");
+        std::vector<int32_t> probe_types;
+        for (const OwnedExpr& e : s.proj) probe_types.push_back(e.root_type());
+        const int kc = check_probe_join(*jd, bridge, probe_types);
         auto js = std::make_shared<JoinStage>();
         js->ls = bridge->impl;
         const LookupSourceImpl& ls = *js->ls;
-        PA_REQUIRE(jd->probe_channel_count == fp.projection_count, PA_ERR_INVALID_ARGUMENT, "the probe page is the projection output");
-        PA_REQUIRE(jd->join_channel_count == 1 && ls.join_channels.size() == 1, PA_ERR_NOT_SUPPORTED, "the fused probe takes one join key");
-        const int kc = jd->probe_join_channels[0];
-        PA_REQUIRE(kc >= 0 && kc < fp.projection_count, PA_ERR_INVALID_ARGUMENT, "probe join channel out of range");
         const int build_key_col = ls.join_channels[0];
-        const int32_t kt = s.proj[kc].root_type();
-        PA_REQUIRE(kt == PA_BIGINT || kt == PA_INTEGER || kt == PA_DATE, PA_ERR_NOT_SUPPORTED, "the fused probe takes a BIGINT / INTEGER / DATE key");
-        PA_REQUIRE(kt == ls.cols[build_key_col].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
         js->key_proj = kc;
         // virtual channels are made for the build columns the aggregation reads
         std::set<int> read;
@@ -71,23 +51,17 @@ Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc&
             auto it = proj_of_build_col.find(col);
             if (it != proj_of_build_col.end()) return it->second;
             const int32_t t = ls.cols[col].type;
-            PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "VARCHAR build columns are not read by the fused probe");
-            // refused here, when the operator is created, so that such a join-aggregation runs as the chain: probe_build_loads has no
-            // load for any other type, and would only say so when the first page generates the kernel
+            // refused here, when the operator is created, so that such a join-aggregation runs as the chain (a REAL build column has a
+            // load, but no aggregation tier was ever run over one)
             PA_REQUIRE(t == PA_BIGINT || t == PA_INTEGER || t == PA_DATE || t == PA_DOUBLE || t == PA_BOOLEAN, PA_ERR_NOT_SUPPORTED,
                        "the fused probe reads BIGINT / INTEGER / DATE / DOUBLE / BOOLEAN build columns");
-            PA_REQUIRE((int)js->build_cols.size() < kMaxBuildChannels, PA_ERR_NOT_SUPPORTED, "the fused probe reads at most 8 build columns");
-            const int v = (int)js->build_cols.size();
-            js->build_cols.push_back(col);
-            js->build_types.push_back(t);
-            s.proj.push_back(input_ref_expr(s.n_in + v, t));
+            const int v = js->add_build_column(col);
+            s.proj.push_back(js->build_column_ref(s.n_in, v));
             return proj_of_build_col[col] = (int)s.proj.size() - 1;
         };
         std::vector<int> build_col_of;  // per channel of the joined page: the build column, or -1 for a probe output
         for (int32_t i = 0; i < jd->probe_output_channel_count; i++) {
-            const int c = jd->probe_output_channels[i];
-            PA_REQUIRE(c >= 0 && c < fp.projection_count, PA_ERR_INVALID_ARGUMENT, "probe output channel out of range");
-            to_proj.push_back(c);
+            to_proj.push_back(jd->probe_output_channels[i]);
             build_col_of.push_back(-1);
         }
         for (int col : ls.output_channels) {

@@ -1,6 +1,7 @@
 // fused_plan.hpp -- what the fused scan-filter-project(-probe)-aggregate operator is asked to do, in the form its code generator
-// (fused_codegen.cpp + one fused_tier_*.cpp per kernel tier) and its host side (op_fused.hpp) share: the plan (Spec), the kernel
-// argument block's host mirror (FusedArgs), the tiers (Variant) and what a generated kernel tells the host about itself (KernelInfo).
+// (fused_codegen.cpp + one fused_tier_*.cpp per kernel tier) and its host side (op_fused.hpp) share: the plan (Spec), the tiers
+// (Variant) and what a generated kernel tells the host about itself (KernelInfo).  The kernels' argument block is PaFusedArgs
+// (kernels/pa_args.h), the one definition the kernels and the host both use.
 #pragma once
 
 #include <map>
@@ -9,62 +10,11 @@
 #include <vector>
 
 #include "exprgen.hpp"
-#include "join_source.hpp"
 #include "operator.hpp"
+#include "probe_stage.hpp"
 
 namespace pa {
 namespace fused {
-
-constexpr int kMaxChannels = 32;  // PA_MAX_CHANNELS in pa_device.h
-constexpr int kMaxBuildChannels = 8;  // PA_MAX_BUILD_CHANNELS
-
-// host mirror of PaFusedArgs (pa_device.h)
-struct FusedArgs {
-    const void* v[kMaxChannels];
-    const int32_t* o[kMaxChannels];
-    const uint8_t* nl[kMaxChannels];
-    int64_t n;
-    int32_t vec;
-    int32_t pad;
-    uint64_t* slab;
-    uint64_t* gt_tag;
-    uint64_t* gt_keys;
-    uint64_t* gt_words;
-    uint32_t gt_mask;
-    int32_t gt_max_fill;
-    int32_t* gt_count;
-    int32_t* err;
-    uint64_t* overflow_rows;
-    const int32_t* row_list;
-    int64_t n_list;
-    int32_t* spill_rows;
-    uint32_t* spill_count;
-    uint32_t gt_rep_mask;
-    uint32_t part_mask;
-    int32_t* gt_rep_count;
-    int32_t* part_ids;
-    int32_t list_blocked;
-    int32_t pad3;
-    uint64_t* sub_tag;
-    uint64_t* sub_keys;
-    uint64_t* sub_words;
-    int32_t* sub_count;
-    const int64_t* part_first;
-    const void* jslots;
-    const uint64_t* jbits;
-    int64_t jmin;
-    uint64_t jrange;
-    uint32_t jmask;
-    int32_t jrows;
-    uint32_t jwrap;
-    uint32_t jpad;
-    const void* bv[kMaxBuildChannels];
-    const uint8_t* bn[kMaxBuildChannels];
-    const void* jrank;
-    const int32_t* jrank_rows;
-    const uint64_t* ranges;
-    int64_t n_ranges;
-};
 
 // V_LDSP: the LDS-table variant with partition-owned tables (see PaFusedArgs::sub_tag)
 // V_BROW: probe stage whose group keys are functions of the build row: the table slot is the build position
@@ -90,12 +40,9 @@ struct KeyPart {
     int null_shift = 0;
 };
 
-// The probe stage between the projections and the aggregation (see the head of the file).
-struct JoinStage {
-    std::shared_ptr<LookupSourceImpl> ls;
+// The probe stage (probe_stage.hpp) between the projections and the aggregation; its build columns are those the aggregation reads.
+struct JoinStage : ProbeStage {
     int key_proj = -1;                 // projection that is the probe join key
-    std::vector<int> build_cols;       // virtual channel n_in + v reads ls->cols[build_cols[v]] at the build position
-    std::vector<int32_t> build_types;
     // per group key: the projection to take it from when the slot is the build position (build columns only: the probe join key
     // is replaced by the build key column, equal on every match); empty = the group keys do not determine / are not determined
     // by the build row, no BROW variant
@@ -175,7 +122,6 @@ struct KernelInfo {
 // thrown by adopt_layout before anything of the page was launched: the page's signature needs another state layout
 struct LayoutChange {};
 
-OwnedExpr input_ref_expr(int32_t channel, int32_t type);
 // jd / bridge: the probe stage between the projections and the aggregation (null: none); the aggregation's channels then index
 // the join's output page = [probe output channels, build output channels] (LookupJoinPageBuilder.java:76-139)
 Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc& ag, const pa_lookup_join_desc* jd = nullptr,

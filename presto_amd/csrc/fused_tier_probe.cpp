@@ -39,18 +39,7 @@ void FusedGen::probe_occupancy_word()
 
 void FusedGen::probe_build_loads()
 {
-    for (size_t v = 0; v < s.join->build_cols.size(); v++) {
-        const std::string id = std::to_string(s.n_in + (int)v), V = std::to_string(v);
-        const int32_t t = s.join->build_types[v];
-        const std::string ct = RowCodegen::ctype(t);
-        build_loads << "const " << ct << " c" << id << " = ";
-        if (t == PA_BIGINT) build_loads << "((const i64*)a.bv[" << V << "])[jb];\n";
-        else if (t == PA_INTEGER || t == PA_DATE) build_loads << "(i64)((const i32*)a.bv[" << V << "])[jb];\n";
-        else if (t == PA_DOUBLE) build_loads << "((const double*)a.bv[" << V << "])[jb];\n";
-        else if (t == PA_BOOLEAN) build_loads << "((const u8*)a.bv[" << V << "])[jb] != 0;\n";
-        else throw Error(PA_ERR_NOT_SUPPORTED, "build column type not read by the fused probe");
-        if (ext[(size_t)s.n_in + v].nullable) build_loads << "const bool cn" << id << " = a.bn[" << V << "] != nullptr && a.bn[" << V << "][jb] != 0;\n";
-    }
+    s.join->emit_build_loads(build_loads, s.n_in, ext);
 }
 
 // loads of the lazy channels of one row into the variables c<C><suffix> (cn<C><suffix>)

@@ -5,11 +5,7 @@
 // hard-coded to 64 (cdna_hip_programming.md section 1).
 #pragma once
 
-typedef long long i64;
-typedef unsigned long long u64;
-typedef int i32;
-typedef unsigned int u32;
-typedef unsigned char u8;
+#include "pa_args.h"
 
 #define PA_WAVE 64
 
@@ -22,7 +18,6 @@ typedef i32 pa_i32x4 __attribute__((ext_vector_type(4)));
 typedef double pa_f64x2 __attribute__((ext_vector_type(2)));
 typedef float pa_f32x4 __attribute__((ext_vector_type(4)));
 typedef i64 pa_i64x2 __attribute__((ext_vector_type(2)));
-typedef u32 pa_u32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------
 // hash arithmetic -- bit-exact with the reference
@@ -287,72 +282,6 @@ __device__ __forceinline__ u32 pa_mix32(u64 k)
 // ---------------------------------------------------------------------------------------------
 // Group tables.  Keys are packed into W 64-bit words (exprgen); equality is word equality.
 // ---------------------------------------------------------------------------------------------
-#define PA_MAX_CHANNELS 32
-#define PA_MAX_BUILD_CHANNELS 8
-
-// Kernel argument block of the fused scan-filter-project-aggregate kernels (op_fused.cpp keeps the
-// host mirror `FusedArgs` in sync).
-struct PaFusedArgs {
-    const void* v[PA_MAX_CHANNELS];   // column values (FLAT) / bytes (VARWIDTH)
-    const i32* o[PA_MAX_CHANNELS];    // VARWIDTH offsets
-    const u8* nl[PA_MAX_CHANNELS];    // nulls (1 B / row) or nullptr
-    i64 n;                            // rows in this page
-    i32 vec;                          // 1: every used buffer is 16-B aligned -> 4 rows / lane / step
-    i32 pad;
-    u64* slab;                        // per-workgroup partial states of this launch
-    u64* gt_tag;                      // global group table: 0 empty | hash<<2|1 busy | hash<<2|3 ready
-    u64* gt_keys;                     // [capacity][W]
-    u64* gt_words;                    // [NW][capacity] accumulator words
-    u32 gt_mask;                      // capacity - 1
-    i32 gt_max_fill;
-    i32* gt_count;                    // groups in the table
-    i32* err;                         // first device-raised pa_status
-    u64* overflow_rows;               // rows that missed the LDS table (drives mode escalation)
-    const i32* row_list;              // GT variant: process these rows (of this launch's range) instead of all n
-    i64 n_list;
-    i32* spill_rows;                  // GT variant: rows whose group did not fit the table (redone after a rehash)
-    u32* spill_count;
-    // Replicas of the group table: workgroup b works on replica b & gt_rep_mask (each a full table of gt_mask + 1 slots,
-    // laid out one after the other in gt_tag / gt_keys / gt_words).  Atomics of many rows on few addresses retire at
-    // ~0.15 M/s per address on this part; R replicas divide the pressure per address by R.  The host folds the
-    // replicas into one table before the result is read.
-    u32 gt_rep_mask;
-    u32 part_mask;                    // hash-partitioning pass: partitions - 1 (partition id part_mask + 1 = row filtered out)
-    i32* gt_rep_count;                // groups of replica r >= 1 at [r]; replica 0 counts in gt_count
-    i32* part_ids;                    // hash-partitioning pass: partition of every row of the launch
-    i32 list_blocked;                 // row_list is cut into one contiguous slice per workgroup (partition-ordered lists)
-    i32 pad3;
-    // Partition-owned tables (LDSP variant): workgroup p aggregates the rows [part_first[p], part_first[p + 1]) of the
-    // partition-ordered columns into an LDS table it LOADS from and STORES to sub_*[p] -- the groups of partition p live nowhere
-    // else, so neither the row loop nor the hand-over to HBM needs an atomic on HBM.  Layout per partition: PA_LC tags,
-    // PA_LC x PA_KW key words, PA_LC x PA_NW accumulator words (slot-major), one group count.
-    u64* sub_tag;
-    u64* sub_keys;
-    u64* sub_words;
-    i32* sub_count;
-    const i64* part_first;
-    // Probe stage (fused FilterAndProject -> LookupJoin -> aggregation over a lookup source with ONE integer key and no
-    // duplicate keys): the keyed probe-side table of join_kernels.hpp (16 B slots: key, head, next), the build side's key
-    // existence bitmap (null = none) and the build columns the aggregation reads, indexed by build position.
-    const void* jslots;
-    const u64* jbits;
-    i64 jmin;
-    u64 jrange;
-    u32 jmask;
-    i32 jrows;                        // build positions (the build-row table of the BROW variant has this many slots)
-    u32 jwrap;                        // probe sequences wrap inside (pos & ~jwrap): jmask, or the partition size - 1 of a partitioned build
-    u32 jpad;
-    const void* bv[PA_MAX_BUILD_CHANNELS];
-    const u8* bn[PA_MAX_BUILD_CHANNELS];
-    // key rank index (join_kernels.hpp JoinRankIndex; null = none, the slot table answers): 16-byte words {64 key bits, build keys
-    // below the word} over [jmin, jmin + jrange], and rank -> build position (null: the rank is the position)
-    const pa_u32x4* jrank;
-    const i32* jrank_rows;
-    // pa_fused_ranges: a table of row ranges taken in place (entry layout: op_fused.cpp range_entry_words)
-    const u64* ranges;
-    i64 n_ranges;
-};
-
 // JoinProbe.getCurrentJoinPosition for a keyed lookup source without duplicate keys (…/operator/join/JoinProbe.java:87-117,
 // PagesHash.getAddressIndex, PagesHash.java:158-170): the build position of key `v`, or -1.  Same walk as
 // k_join_probe_count_keyed (join_kernels.hip): bitmap first -- most probe rows of a selective join miss, and a clustered probe
@@ -942,37 +871,6 @@ __device__ __forceinline__ i32 pa_block_exclusive_scan_256(i32 v, i32* total)
     return base + inc - v;
 }
 
-// Kernel argument block of the generated FilterAndProject kernels (op_filter_project.cpp mirrors it).
-struct PaFpArgs {
-    const void* v[PA_MAX_CHANNELS];
-    const i32* o[PA_MAX_CHANNELS];
-    const u8* nl[PA_MAX_CHANNELS];
-    void* out_v[PA_MAX_CHANNELS];   // per projection: output values (worst case n entries)
-    u8* out_nl[PA_MAX_CHANNELS];    // per projection: output nulls or nullptr
-    i64 n;
-    i32 vec;
-    i32 pad;
-    u8* sel4;                       // 4 selection bits per row quad (filter result, PageFilter.filter)
-    i32* tile_counts;               // selected rows per 1024-row tile
-    const i32* tile_offsets;        // exclusive scan of tile_counts
-    i32* positions;                 // SelectedPositions.positions (ascending), worst case n entries
-    i32* err;
-    const u64* dyn_bits;            // dynamic filter from a join's build side: existence bitmap over [dyn_min, dyn_min + dyn_range]
-    i64 dyn_min;
-    u64 dyn_range;
-    // probe stage (FilterAndProject -> LookupJoin in one pass, op_filter_project.cpp): the keyed probe-side table, its key bitmap,
-    // and the build columns the output carries, as in PaFusedArgs
-    const void* jslots;
-    const u64* jbits;
-    i64 jmin;
-    u64 jrange;
-    u32 jmask;
-    u32 jwrap;
-    const void* bv[PA_MAX_BUILD_CHANNELS];
-    const u8* bn[PA_MAX_BUILD_CHANNELS];
-    const pa_u32x4* jrank;          // key rank index, as in PaFusedArgs
-    const i32* jrank_rows;
-};
 // can a probe row with this key match any build row?  (exact inside the bitmap's range; NULL keys never match)
 __device__ __forceinline__ bool pa_dyn_test(const PaFpArgs& a, const i64 key)
 {

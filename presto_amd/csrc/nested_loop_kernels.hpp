@@ -11,8 +11,7 @@ namespace pa {
 constexpr int kNestedLoopLdsChunk = 1024;
 // ... when one chunk of all of them fits into this much LDS (3 workgroups of 256 threads per CU); else they are read from memory
 constexpr int kNestedLoopLdsBytes = 48 << 10;
-// channels of the build page and the probe page together (the argument block of the pair kernels has one slot per channel)
-constexpr int kNestedLoopMaxChannels = 64;
+// (channels of the build page and the probe page together: PA_NL_MAX_CHANNELS, with the pair kernels' argument block in kernels/pa_args.h)
 
 // The plain product of the probe rows [i0, i0 + n) with the build rows [j0, j0 + m), probe-major: for t in [0, n * m)
 // probe_idx[t] = i0 + t / m, build_pos[t] = j0 + t % m.  n * m < 2^31.

@@ -24,17 +24,15 @@
 
 #include "exprgen.hpp"
 #include "jit.hpp"
-#include "join_source.hpp"
 #include "operator.hpp"
 #include "position_gather.hpp"
+#include "probe_stage.hpp"
 #include "rowgen.hpp"
 #include "scan_kernels.hpp"
 
 namespace pa {
 namespace {
 
-constexpr int kMaxChannels = 32;
-constexpr int kMaxBuildChannels = 8;  // PA_MAX_BUILD_CHANNELS
 // A workgroup of 256 threads handles kTileQuads x 256 row quads.  More than one quad per thread (fewer, longer workgroups,
 // all loads in flight before the first block scan) was measured SLOWER on MI355X -- page -> page over 2^27 rows, 1 / 2 / 4 / 8
 // quads: Q6 filter 155 / 146 / 147 / 147 G rows/s, Q1 filter (96 % pass) 106 / 92 / 80 / 79 G, Q3 per step 27.8 / 28.5 / 29.1 /
@@ -55,48 +53,12 @@ static const int kTileRows = 1024 * kTileQuads;
 // same-address device-scope atomic (about 8 ns each, executed at the memory side) and three of four waves idle during the
 // look-back; re-reading the selected quads and probing them a second time costs less.
 
-struct FpArgs {  // host mirror of PaFpArgs
-    const void* v[kMaxChannels];
-    const int32_t* o[kMaxChannels];
-    const uint8_t* nl[kMaxChannels];
-    void* out_v[kMaxChannels];
-    uint8_t* out_nl[kMaxChannels];
-    int64_t n;
-    int32_t vec;
-    int32_t pad;
-    uint8_t* sel4;
-    int32_t* tile_counts;
-    const int32_t* tile_offsets;
-    int32_t* positions;
-    int32_t* err;
-    const uint64_t* dyn_bits;
-    int64_t dyn_min;
-    uint64_t dyn_range;
-    const void* jslots;
-    const uint64_t* jbits;
-    int64_t jmin;
-    uint64_t jrange;
-    uint32_t jmask;
-    uint32_t jwrap;
-    const void* bv[kMaxBuildChannels];
-    const uint8_t* bn[kMaxBuildChannels];
-    const void* jrank;
-    const int32_t* jrank_rows;
-};
-
-// Probe stage (FilterAndProject -> LookupJoin (INNER) in one pass; pa_fused_join_create): a row is selected when the filter keeps it
-// AND its key finds a build row -- the lookup source has one integer key without duplicates, so at most one -- and the output page
-// is [probe output channels (projections), build output channels]: the build columns are "virtual" channels n_in + v of the
-// generated code, read at the build position (as in the probe stage of op_fused_launch.cpp).
-struct FpJoin {
-    std::shared_ptr<LookupSourceImpl> ls;
-    OwnedExpr key;                  // the probe join key (a projection of the FilterAndProject)
-    std::vector<int> build_cols;    // virtual channel n_in + v = ls->cols[build_cols[v]]
-    std::vector<int32_t> build_types;
-};
-
 struct FpSpec {
-    std::shared_ptr<FpJoin> join;
+    // Probe stage (probe_stage.hpp; FilterAndProject -> LookupJoin (INNER) in one pass, pa_fused_join_create): a row is selected when the
+    // filter keeps it AND its key finds a build row, and the output page is [probe output channels (projections), build output
+    // channels] -- every build output channel is a build column of the stage.  Null: none.
+    std::shared_ptr<ProbeStage> join;
+    OwnedExpr join_key;            // the probe join key (a projection of the FilterAndProject)
     int n_in = 0;
     std::vector<int32_t> in_types;
     bool has_filter = false;
@@ -120,8 +82,8 @@ FpSpec make_fp_spec(const pa_filter_project_desc* d)
 {
     PA_REQUIRE(d != nullptr, PA_ERR_INVALID_ARGUMENT, "descriptor is null");
     FpSpec s;
-    PA_REQUIRE(d->input_channel_count >= 0 && d->input_channel_count <= kMaxChannels, PA_ERR_NOT_SUPPORTED, "at most 32 input channels");
-    PA_REQUIRE(d->projection_count >= 0 && d->projection_count <= kMaxChannels, PA_ERR_NOT_SUPPORTED, "at most 32 projections");
+    PA_REQUIRE(d->input_channel_count >= 0 && d->input_channel_count <= PA_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED, "at most 32 input channels");
+    PA_REQUIRE(d->projection_count >= 0 && d->projection_count <= PA_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED, "at most 32 projections");
     s.n_in = d->input_channel_count;
     if (s.n_in) s.in_types.assign(d->input_types, d->input_types + s.n_in);
     s.has_filter = d->filter != nullptr;
@@ -152,51 +114,27 @@ FpSpec make_fp_spec(const pa_filter_project_desc* d)
 // FilterAndProject's projections, then the build output channels
 FpSpec make_fp_join_spec(const pa_filter_project_desc* fp, const pa_lookup_join_desc* jd, pa_lookup_source* bridge)
 {
-    PA_REQUIRE(fp != nullptr && jd != nullptr && bridge != nullptr && bridge->impl != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
+    PA_REQUIRE(fp != nullptr && jd != nullptr && bridge != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
     FpSpec base = make_fp_spec(fp);
-    PA_REQUIRE(jd->join_type == PA_JOIN_INNER && jd->filter == nullptr, PA_ERR_NOT_SUPPORTED, "the fused probe is an inner join without a filter function");
-    auto js = std::make_shared<FpJoin>();
+    std::vector<int32_t> probe_types;
+    for (const OwnedExpr& e : base.proj) probe_types.push_back(e.root_type());
+    const int kc = check_probe_join(*jd, bridge, probe_types);
+    auto js = std::make_shared<ProbeStage>();
     js->ls = bridge->impl;
-    const LookupSourceImpl& ls = *js->ls;
-    PA_REQUIRE(jd->probe_channel_count == (int32_t)base.proj.size(), PA_ERR_INVALID_ARGUMENT, "the probe page is the projection output");
-    PA_REQUIRE(jd->join_channel_count == 1 && ls.join_channels.size() == 1, PA_ERR_NOT_SUPPORTED, "the fused probe takes one join key");
-    const int kc = jd->probe_join_channels[0];
-    PA_REQUIRE(kc >= 0 && kc < (int)base.proj.size(), PA_ERR_INVALID_ARGUMENT, "probe join channel out of range");
-    const int32_t kt = base.proj[(size_t)kc].root_type();
-    PA_REQUIRE(kt == PA_BIGINT || kt == PA_INTEGER || kt == PA_DATE, PA_ERR_NOT_SUPPORTED, "the fused probe takes a BIGINT / INTEGER / DATE key");
-    PA_REQUIRE(kt == ls.cols[(size_t)ls.join_channels[0]].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
-    js->key = base.proj[(size_t)kc];
     FpSpec s = base;
+    s.join_key = base.proj[(size_t)kc];
     s.proj.clear();
-    for (int32_t i = 0; i < jd->probe_output_channel_count; i++) {
-        const int c = jd->probe_output_channels[i];
-        PA_REQUIRE(c >= 0 && c < (int)base.proj.size(), PA_ERR_INVALID_ARGUMENT, "probe output channel out of range");
-        s.proj.push_back(base.proj[(size_t)c]);
+    for (int32_t i = 0; i < jd->probe_output_channel_count; i++) s.proj.push_back(base.proj[(size_t)jd->probe_output_channels[i]]);
+    for (int col : js->ls->output_channels) {
+        const int v = js->add_build_column(col);
+        s.proj.push_back(js->build_column_ref(s.n_in, v));
     }
-    for (int col : ls.output_channels) {
-        const int32_t t = ls.cols[(size_t)col].type;
-        PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "VARCHAR build columns are not carried by the fused probe");
-        // (said here, not by the code generator at the first page: the operator chain carries them)
-        PA_REQUIRE(t != PA_DECIMAL && t != PA_LONG_DECIMAL, PA_ERR_NOT_SUPPORTED, "DECIMAL build columns are not carried by the fused probe");
-        PA_REQUIRE((int)js->build_cols.size() < kMaxBuildChannels, PA_ERR_NOT_SUPPORTED, "the fused probe carries at most 8 build columns");
-        OwnedExpr e;
-        pa_expr_node node{};
-        node.kind = PA_EXPR_INPUT_REF;
-        node.type = t;
-        node.channel = s.n_in + (int)js->build_cols.size();
-        e.nodes.push_back(node);
-        e.strings.emplace_back();
-        e.root = 0;
-        s.proj.push_back(std::move(e));
-        js->build_cols.push_back(col);
-        js->build_types.push_back(t);
-    }
-    PA_REQUIRE(s.proj.size() <= (size_t)kMaxChannels, PA_ERR_NOT_SUPPORTED, "at most 32 output channels");
+    PA_REQUIRE(s.proj.size() <= (size_t)PA_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED, "at most 32 output channels");
     s.has_filter = true;  // the probe selects
     s.join = js;
     std::set<int32_t> used;
     if (s.filter.root >= 0 && fp->filter != nullptr) s.filter.collect_channels(&used);
-    js->key.collect_channels(&used);
+    s.join_key.collect_channels(&used);
     for (const auto& e : s.proj) e.collect_channels(&used);
     s.used_channel.assign(s.n_in, false);
     for (int32_t c : used) {
@@ -205,18 +143,9 @@ FpSpec make_fp_join_spec(const pa_filter_project_desc* fp, const pa_lookup_join_
     return s;
 }
 
-FpKernelInfo generate_fp(const FpSpec& s, const std::vector<ChannelLayout>& layout_in)
+// layout: the page's channels and, behind them, the build columns of the probe stage (ProbeStage::append_build_channels)
+FpKernelInfo generate_fp(const FpSpec& s, const std::vector<ChannelLayout>& layout)
 {
-    // (probe stage: the build columns as channels n_in + v; the caller may have appended them already, with their nullability)
-    std::vector<ChannelLayout> layout(layout_in.begin(), layout_in.begin() + s.n_in);
-    if (s.join) {
-        for (size_t v = 0; v < s.join->build_cols.size(); v++) {
-            ChannelLayout cl;
-            cl.type = s.join->build_types[v];
-            cl.nullable = (size_t)s.n_in + v < layout_in.size() ? layout_in[(size_t)s.n_in + v].nullable : true;
-            layout.push_back(cl);
-        }
-    }
     FpKernelInfo k;
     RowInputs ri;
     ri.n_in = s.n_in;
@@ -250,7 +179,7 @@ FpKernelInfo generate_fp(const FpSpec& s, const std::vector<ChannelLayout>& layo
     std::string key_expr;
     if (s.join) {
         RowCodegen gen(layout, "a.err");
-        GenValue kv = gen.emit(s.join->key, key_code);
+        GenValue kv = gen.emit(s.join_key, key_code);
         key_expr = "(u64)(i64)" + kv.v;
         if (probing) {
             src << "if (!keep) return false;\n" << key_code.str();
@@ -279,21 +208,7 @@ FpKernelInfo generate_fp(const FpSpec& s, const std::vector<ChannelLayout>& layo
     // projections of one selected row written at output position `rank`
     src << "__device__ __forceinline__ void pa_out(const PaFpArgs& a, i64 rank, i32 row" << (s.join ? ", i32 jb" : "") << params << ")\n{\n";
     src << "if (a.positions) a.positions[rank] = row;\n";
-    if (s.join) {
-        // the build columns of the output at the row's build position
-        for (size_t v = 0; v < s.join->build_cols.size(); v++) {
-            const std::string id = std::to_string(s.n_in + (int)v), V = std::to_string(v);
-            const int32_t t = s.join->build_types[v];
-            src << "const " << RowCodegen::ctype(t) << " c" << id << " = ";
-            if (t == PA_BIGINT) src << "((const i64*)a.bv[" << V << "])[jb];\n";
-            else if (t == PA_INTEGER || t == PA_DATE) src << "(i64)((const i32*)a.bv[" << V << "])[jb];\n";
-            else if (t == PA_DOUBLE) src << "((const double*)a.bv[" << V << "])[jb];\n";
-            else if (t == PA_REAL) src << "((const float*)a.bv[" << V << "])[jb];\n";
-            else if (t == PA_BOOLEAN) src << "((const u8*)a.bv[" << V << "])[jb] != 0;\n";
-            else throw Error(PA_ERR_NOT_SUPPORTED, "build column type not carried by the fused probe");
-            if (layout[(size_t)s.n_in + v].nullable) src << "const bool cn" << id << " = a.bn[" << V << "] != nullptr && a.bn[" << V << "][jb] != 0;\n";
-        }
-    }
+    if (s.join) s.join->emit_build_loads(src, s.n_in, layout);  // the build columns of the output at the row's build position
     {
         RowCodegen gen(layout, "a.err");
         std::ostringstream body;
@@ -480,32 +395,13 @@ public:
         std::vector<ChannelLayout> layout(sp.n_in);
         std::string sig;
         bool vec = true;
-        FpArgs a;
+        PaFpArgs a;
         memset(&a, 0, sizeof a);
         bind_inputs(sp, in_, &layout, &sig, &vec, &a);
         if (spec_.join) {
-            const LookupSourceImpl& ls = *spec_.join->ls;
-            PA_REQUIRE(ls.built.load(), PA_ERR_ILLEGAL_STATE, "probe page before the lookup source was built");
-            if (int32_t e = ls.error.load()) throw Error(e, "hash build failed on device");
-            PA_REQUIRE(ls.keyed && !ls.has_duplicates, PA_ERR_ILLEGAL_STATE, "internal: fused probe over a lookup source with duplicate keys");
-            a.jslots = ls.key_slots.ptr();
-            a.jmask = ls.probe_mask;
-            a.jwrap = ls.probe_wrap;
-            a.jbits = ls.bitmap.bits;
-            a.jmin = ls.bitmap.min_key;
-            a.jrange = ls.bitmap.range;
-            a.jrank = ls.rank.words;
-            a.jrank_rows = ls.rank.rows;
-            for (size_t v = 0; v < spec_.join->build_cols.size(); v++) {
-                const BuildColumn& bc = ls.cols[(size_t)spec_.join->build_cols[v]];
-                a.bv[v] = bc.values.ptr();
-                a.bn[v] = bc.has_nulls ? bc.nulls.as<uint8_t>() : nullptr;
-                ChannelLayout cl;
-                cl.type = spec_.join->build_types[v];
-                cl.nullable = bc.has_nulls;
-                layout.push_back(cl);
-                sig += cl.nullable ? 'N' : '_';
-            }
+            spec_.join->require_built();
+            fill_probe_args(a, *spec_.join);
+            spec_.join->append_build_channels(&layout, &sig);
         }
         const Compiled& ck = kernel_for(external ? 2 : 0, sig, layout);
         cur_ = &ck;
@@ -798,7 +694,7 @@ private:
         f << '|';
         for (bool u : sp.used_channel) f << (u ? '1' : '0');
         if (sp.join) {
-            f << "|J" << sp.join->key.fingerprint() << ':';
+            f << "|J" << sp.join_key.fingerprint() << ':';
             for (size_t v = 0; v < sp.join->build_cols.size(); v++) f << sp.join->build_cols[v] << '/' << sp.join->build_types[v] << ',';
         }
         f << "|q" << kTileQuads;
@@ -845,7 +741,7 @@ private:
     }
 
     // column pointers, layout signature and alignment of the channels `sp` reads
-    static void bind_inputs(const FpSpec& sp, const DevPage& in, std::vector<ChannelLayout>* layout, std::string* sig, bool* vec, FpArgs* a)
+    static void bind_inputs(const FpSpec& sp, const DevPage& in, std::vector<ChannelLayout>* layout, std::string* sig, bool* vec, PaFpArgs* a)
     {
         for (int c = 0; c < sp.n_in; c++) {
             ChannelLayout& l = (*layout)[c];
@@ -886,7 +782,7 @@ private:
         std::vector<ChannelLayout> layout(spec_.n_in);
         std::string sig;
         bool vec = true;
-        FpArgs a;
+        PaFpArgs a;
         memset(&a, 0, sizeof a);
         bind_inputs(dict_spec_, d, &layout, &sig, &vec, &a);
         const Compiled& dk = kernel_for(1, sig, layout);
@@ -988,6 +884,8 @@ std::string filter_project_probe_source_for_desc(const pa_fused_join_desc* desc,
     FpSpec s = make_fp_join_spec(&desc->filter_project, &desc->join, &bridge);
     std::vector<ChannelLayout> layout(s.n_in);
     for (int c = 0; c < s.n_in; c++) layout[c].type = s.in_types[c];
+    s.join->append_build_channels(&layout);
+    for (size_t c = (size_t)s.n_in; c < layout.size(); c++) layout[c].nullable = true;  // (shown: the form that also reads the NULL flags)
     return generate_fp(s, layout).source;
 }
 

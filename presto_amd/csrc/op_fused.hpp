@@ -240,7 +240,7 @@ private:
     void flush_ranges();
     void process_ranges(const std::shared_ptr<const std::vector<DevPage>>& set, int64_t rows);
     static bool range_aligned(const DevPage& r, const std::vector<bool>& used);
-    int64_t fill_range_table(const KernelInfo& ki, const DevPage& dp, FusedArgs& a, hipStream_t s);
+    int64_t fill_range_table(const KernelInfo& ki, const DevPage& dp, PaFusedArgs& a, hipStream_t s);
 
     // ==== launches: kernel cache, staged loads, the tiers (op_fused_launch.cpp) ==========================================
     void add_page(const pa_page* page);
@@ -262,15 +262,14 @@ private:
     // ---- one page through one tier: run_page fills the arguments every tier shares and hands over to the tier's launcher ----
     // (false: the tier gave up -- resume_from_ says from which row the tier mode_ now names takes over, see run_tiers)
     bool run_page(const Compiled& ck, const DevPage& dp, bool vec, const RowList* list = nullptr, int64_t start_row = 0);
-    void fill_join_args(FusedArgs& a) const;
-    void advance_columns(FusedArgs& a, const DevPage& dp, int64_t offset) const;
-    bool run_page_build_rows(const Compiled& ck, const DevPage& dp, FusedArgs a, int64_t start_row);
-    bool launch_global(const Compiled& ck, const DevPage& dp, FusedArgs& a, int64_t offset, int64_t total, int64_t range_entries);
-    bool launch_lds(const Compiled& ck, const DevPage& dp, FusedArgs& a, bool vec, int64_t offset, int64_t total, int64_t range_entries);
-    bool launch_table(const Compiled& ck, const DevPage& dp, FusedArgs& a, const RowList* list, int64_t offset, int64_t total);
+    void advance_columns(PaFusedArgs& a, const DevPage& dp, int64_t offset) const;
+    bool run_page_build_rows(const Compiled& ck, const DevPage& dp, PaFusedArgs a, int64_t start_row);
+    bool launch_global(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, int64_t offset, int64_t total, int64_t range_entries);
+    bool launch_lds(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, bool vec, int64_t offset, int64_t total, int64_t range_entries);
+    bool launch_table(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, const RowList* list, int64_t offset, int64_t total);
     int grid_for(const KernelInfo& ki, int64_t work, const RowList* list) const;
     uint32_t replicas_for(const KernelInfo& ki, int grid, const RowList* list) const;
-    FusedArgs replay_args(const FusedArgs& a, uint32_t spilled, int cur, uint64_t flush_room);
+    PaFusedArgs replay_args(const PaFusedArgs& a, uint32_t spilled, int cur, uint64_t flush_room);
     // ---- late confirmation of the few-groups launches ----
     static constexpr size_t kMaxInflight = 2;
     int32_t* h_ctl_lds(int b) const { return h_ctl_ + 16 + 8 * b; }

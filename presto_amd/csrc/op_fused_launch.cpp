@@ -29,10 +29,7 @@ void FusedAggregationOperator::add_page(const pa_page* page)
         dict_keys.push_back(c);
     }
     if (spec_.join && !join_checked_) {
-        const LookupSourceImpl& ls = *spec_.join->ls;
-        PA_REQUIRE(ls.built.load(), PA_ERR_ILLEGAL_STATE, "probe page before the lookup source was built");
-        if (int32_t e = ls.error.load()) throw Error(e, "hash build failed on device");
-        PA_REQUIRE(ls.keyed && !ls.has_duplicates, PA_ERR_ILLEGAL_STATE, "internal: fused probe over a lookup source with duplicate keys");
+        spec_.join->require_built();
         join_checked_ = true;
         // the group is the build row whenever the plan allows it: no hashing, no key compares, no spills
         if (grouped_ && !spec_.join->brow_group_proj.empty() && !getenv("PRESTO_AMD_NO_BROW")) mode_ = V_BROW;
@@ -58,15 +55,7 @@ void FusedAggregationOperator::add_page(const pa_page* page)
         }
         sig += layout[c].nullable ? 'n' : '-';
     }
-    if (spec_.join) {  // the build columns as channels n_in + v: their nullability is the lookup source's, fixed since the build
-        for (size_t v = 0; v < spec_.join->build_cols.size(); v++) {
-            ChannelLayout cl;
-            cl.type = spec_.join->build_types[v];
-            cl.nullable = spec_.join->ls->cols[spec_.join->build_cols[v]].has_nulls;
-            layout.push_back(cl);
-            sig += cl.nullable ? 'N' : '_';
-        }
-    }
+    if (spec_.join) spec_.join->append_build_channels(&layout, &sig);
     run_tiers(sig, layout, dp, vec, 0);
 }
 
@@ -117,29 +106,9 @@ void FusedAggregationOperator::run_tiers(const std::string& sig, const std::vect
     }
 }
 
-void FusedAggregationOperator::fill_join_args(FusedArgs& a) const
-{
-    const JoinStage& js = *spec_.join;
-    const LookupSourceImpl& ls = *js.ls;
-    a.jslots = ls.key_slots.ptr();
-    a.jmask = ls.probe_mask;
-    a.jwrap = ls.probe_wrap;
-    a.jbits = ls.bitmap.bits;
-    a.jmin = ls.bitmap.min_key;
-    a.jrange = ls.bitmap.range;
-    a.jrank = ls.rank.words;
-    a.jrank_rows = ls.rank.rows;
-    a.jrows = ls.n;
-    for (size_t v = 0; v < js.build_cols.size(); v++) {
-        const BuildColumn& bc = ls.cols[js.build_cols[v]];
-        a.bv[v] = bc.values.ptr();
-        a.bn[v] = bc.has_nulls ? bc.nulls.as<uint8_t>() : nullptr;
-    }
-}
-
 // BROW: accumulators indexed by build position.  The table has one slot per build row -- it never fills, nothing spills,
 // nothing needs confirming: launches are enqueued and forgotten (the error word is read at finish).
-bool FusedAggregationOperator::run_page_build_rows(const Compiled& ck, const DevPage& dp, FusedArgs a, int64_t start_row)
+bool FusedAggregationOperator::run_page_build_rows(const Compiled& ck, const DevPage& dp, PaFusedArgs a, int64_t start_row)
 {
     HostTraceScope trace("    fused.run_page_build_rows");
     hipStream_t s = stream_.get();
@@ -193,7 +162,7 @@ bool FusedAggregationOperator::run_page_build_rows(const Compiled& ck, const Dev
 }
 
 // the column pointers of `a` moved to row `offset` of the page
-void FusedAggregationOperator::advance_columns(FusedArgs& a, const DevPage& dp, int64_t offset) const
+void FusedAggregationOperator::advance_columns(PaFusedArgs& a, const DevPage& dp, int64_t offset) const
 {
     if (offset <= 0) return;
     for (int c = 0; c < spec_.n_in; c++) {
@@ -213,7 +182,7 @@ bool FusedAggregationOperator::run_page(const Compiled& ck, const DevPage& dp, b
     hipStream_t s = stream_.get();
     const KernelInfo& ki = ck.info;
     last_info_ = &ki;
-    FusedArgs a;
+    PaFusedArgs a;
     memset(&a, 0, sizeof a);
     for (int c = 0; c < spec_.n_in; c++) {
         if (!spec_.used_channel[c]) continue;
@@ -225,7 +194,10 @@ bool FusedAggregationOperator::run_page(const Compiled& ck, const DevPage& dp, b
     a.err = ctl_;
     a.gt_count = ctl_ + 1;
     a.overflow_rows = reinterpret_cast<uint64_t*>(ctl_ + 2);
-    if (spec_.join) fill_join_args(a);
+    if (spec_.join) {
+        fill_probe_args(a, *spec_.join);
+        a.jrows = spec_.join->ls->n;
+    }
     if (ki.variant == V_BROW) return run_page_build_rows(ck, dp, a, start_row);
     // a table of ranges: one launch takes all of them, a workgroup per entry at a time
     int64_t range_entries = 0;
@@ -242,7 +214,7 @@ bool FusedAggregationOperator::run_page(const Compiled& ck, const DevPage& dp, b
 
 // Ungrouped tier (V_GLOBAL, its range-table and staged forms): one launch over rows [offset, total), one partial state per workgroup
 // in the slab, merged into the state in a fixed order.
-bool FusedAggregationOperator::launch_global(const Compiled& ck, const DevPage& dp, FusedArgs& a, int64_t offset, int64_t total, int64_t range_entries)
+bool FusedAggregationOperator::launch_global(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, int64_t offset, int64_t total, int64_t range_entries)
 {
     if (offset >= total) return true;
     hipStream_t s = stream_.get();
@@ -273,7 +245,7 @@ bool FusedAggregationOperator::launch_global(const Compiled& ck, const DevPage& 
 
 // Few-groups tier (V_LDS and its range-table form): per-wave partial tables in one of two slabs, merged into the HBM table on a
 // second stream while the next launch streams; every launch is confirmed late (confirm_oldest).
-bool FusedAggregationOperator::launch_lds(const Compiled& ck, const DevPage& dp, FusedArgs& a, bool vec, int64_t offset, int64_t total,
+bool FusedAggregationOperator::launch_lds(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, bool vec, int64_t offset, int64_t total,
                                           int64_t range_entries)
 {
     hipStream_t s = stream_.get();
@@ -421,9 +393,9 @@ uint32_t FusedAggregationOperator::replicas_for(const KernelInfo& ki, int grid, 
 }
 
 // the arguments of the launch that replays the `spilled` rows listed in spill[cur], on the table as ensure_table has just left it
-FusedArgs FusedAggregationOperator::replay_args(const FusedArgs& a, uint32_t spilled, int cur, uint64_t flush_room)
+PaFusedArgs FusedAggregationOperator::replay_args(const PaFusedArgs& a, uint32_t spilled, int cur, uint64_t flush_room)
 {
-    FusedArgs r = a;
+    PaFusedArgs r = a;
     r.n = 0;
     if (r.list_blocked == 2) r.list_blocked = 1;  // the spilled rows are a real list
     r.row_list = gt_.spill[cur].as<int32_t>();
@@ -439,7 +411,7 @@ FusedArgs FusedAggregationOperator::replay_args(const FusedArgs& a, uint32_t spi
 
 // Table tiers (V_GT: the HBM table itself; V_LDSH / V_LDSP: workgroup-level LDS tables in front of it): launches of at most 2^26
 // rows, each followed by the replay of the rows whose group found no room, and by the decision which tier takes the rows behind it.
-bool FusedAggregationOperator::launch_table(const Compiled& ck, const DevPage& dp, FusedArgs& a, const RowList* list, int64_t offset, int64_t total)
+bool FusedAggregationOperator::launch_table(const Compiled& ck, const DevPage& dp, PaFusedArgs& a, const RowList* list, int64_t offset, int64_t total)
 {
     hipStream_t s = stream_.get();
     const KernelInfo& ki = ck.info;
@@ -562,7 +534,7 @@ bool FusedAggregationOperator::launch_table(const Compiled& ck, const DevPage& d
             PA_HIP(hipMemsetAsync(ctl_ + 6, 0, 4, s));
             // at least twice the slots (ensure_table doubles its argument)
             ensure_table(std::max<uint64_t>((uint64_t)gt_.cap / 2 + 1, gt_.groups_upper + spilled) + flush_room);
-            FusedArgs r = replay_args(a, spilled, cur, flush_room);
+            PaFusedArgs r = replay_args(a, spilled, cur, flush_room);
             void* rparams[] = {&r};
             // (never more workgroups than the launch the table was sized for: V_LDSH flushes per workgroup)
             // partition-owned tables: the spilled rows are a list over all partitions -- they go to the HBM table, through its kernel

@@ -278,9 +278,10 @@ bool FusedAggregationOperator::fetch_result(const KernelInfo& ki, std::vector<ui
         if (build_rows_table_) {
             // build-row table: no kernel counted its groups, and its key words are still to be written -- once per group, from
             // the build columns (pa_brow_keys)
-            FusedArgs a;
+            PaFusedArgs a;
             memset(&a, 0, sizeof a);
-            fill_join_args(a);
+            fill_probe_args(a, *spec_.join);
+            a.jrows = spec_.join->ls->n;
             a.err = ctl_;
             a.gt_count = ctl_ + 1;
             PA_HIP(hipMemsetAsync(ctl_ + 1, 0, 4, s));

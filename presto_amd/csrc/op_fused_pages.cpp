@@ -359,7 +359,7 @@ void FusedAggregationOperator::append_to_arena(const pa_page* page)
             if (a.nullable[c]) a.nulls[c].ensure((size_t)kArenaRows);
         }
     }
-    CopySeg now[3 * kMaxChannels];
+    CopySeg now[3 * PA_MAX_CHANNELS];
     VarSeg vnow[kInlineVarSegs];
     int m = 0, vm = 0, slot = 0;
     // the device cursors of this append: read from one half of a.cursors, left in the other (deferred appends of one
@@ -536,7 +536,7 @@ void FusedAggregationOperator::flush_arena()
 
 // The table of a ranged launch (entry layout: range_entry_words): every range cut into entries of at most kRangeRows rows,
 // each with its own buffer addresses.  Returns the number of entries.
-int64_t FusedAggregationOperator::fill_range_table(const KernelInfo& ki, const DevPage& dp, FusedArgs& a, hipStream_t s)
+int64_t FusedAggregationOperator::fill_range_table(const KernelInfo& ki, const DevPage& dp, PaFusedArgs& a, hipStream_t s)
 {
     const std::vector<ChannelLayout>& layout = *cur_layout_;
     const int rw = range_entry_words(spec_, layout);

@@ -218,7 +218,7 @@ void FusedAggregationOperator::run_page_partitioned(const std::string& sig, cons
     const int64_t chunk = (int64_t)1 << 26;
     for (int64_t offset = start_row; offset < dp.n; offset += chunk) {
         const int64_t n = std::min(chunk, dp.n - offset);
-        FusedArgs a;
+        PaFusedArgs a;
         memset(&a, 0, sizeof a);
         for (int c = 0; c < spec_.n_in; c++) {
             if (!spec_.used_channel[c]) continue;

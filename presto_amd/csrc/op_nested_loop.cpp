@@ -35,6 +35,8 @@
 #include "exprgen.hpp"
 #include "held_rows.hpp"
 #include "jit.hpp"
+#define PA_ARGS_STDINT
+#include "kernels/pa_args.h"
 #include "keyed_operator.hpp"
 #include "nested_loop_kernels.hpp"
 #include "rowgen.hpp"
@@ -69,18 +71,6 @@ namespace {
 // variant 1 has idle lanes in its only step, and variant 0 was never behind (16 build rows: 0.70-1.01 of variant 1's time).
 constexpr int64_t kNestedLoopRowsForVariant0 = (int64_t)1 << 18;
 constexpr int64_t kNestedLoopBuildRowsForVariant1 = 64;
-
-struct NlArgs {  // host mirror of PaNlArgs (generated below)
-    const void* v[kNestedLoopMaxChannels];
-    const int32_t* o[kNestedLoopMaxChannels];
-    const uint8_t* nl[kNestedLoopMaxChannels];
-    int32_t i0, n, j0, m;
-    int32_t* counts;
-    const int32_t* offsets;
-    int32_t* probe_idx;
-    int32_t* build_pos;
-    int32_t* err;
-};
 
 bool known_type(int32_t t) { return t >= PA_BIGINT && t <= PA_LONG_DECIMAL; }
 
@@ -150,8 +140,6 @@ std::string generate_nl(const NlPlan& p, const std::vector<ChannelLayout>& layou
     ri.used = p.used;
     ri.short_bound.assign(ri.n_in, 0);
     std::ostringstream src;
-    src << "struct PaNlArgs {\n    const void* v[" << kNestedLoopMaxChannels << "];\n    const i32* o[" << kNestedLoopMaxChannels << "];\n    const u8* nl["
-        << kNestedLoopMaxChannels << "];\n    i32 i0, n, j0, m;\n    i32* counts;\n    const i32* offsets;\n    i32* probe_idx;\n    i32* build_pos;\n    i32* err;\n};\n";
     // the predicate over one pair: TRUE keeps it, NULL counts as false (PageFunctionCompiler.java:539-542)
     src << "__device__ __forceinline__ bool pa_nl_keep(const PaNlArgs& a" << row_params(ri, layout) << ")\n{\n";
     {
@@ -277,7 +265,7 @@ void* checked_stream(const pa_nested_loop_build_desc* d)
     PA_REQUIRE(d->input_channel_count >= 0, PA_ERR_INVALID_ARGUMENT, "negative build channel count");
     PA_REQUIRE(d->input_channel_count == 0 || d->input_types != nullptr, PA_ERR_INVALID_ARGUMENT, "build types are null");
     check_types_known(d->input_types, d->input_channel_count, "build");
-    PA_REQUIRE(d->input_channel_count <= kNestedLoopMaxChannels, PA_ERR_NOT_SUPPORTED, "at most 64 build channels");
+    PA_REQUIRE(d->input_channel_count <= PA_NL_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED, "at most 64 build channels");
     for (int32_t c = 0; c < d->input_channel_count; c++) check_carried_type(d->input_types[c], "build");
     return d->stream;
 }
@@ -382,7 +370,7 @@ NlPlan check_join(const pa_nested_loop_join_desc* d, const std::vector<int32_t>&
     check_types_carried(probe_types, "probe");
     check_types_carried(build_types, "build");
     PA_REQUIRE(d->probe_output_channel_count + d->build_output_channel_count > 0, PA_ERR_NOT_SUPPORTED, "a nested-loop join without output channels is not on the device path");
-    PA_REQUIRE((int64_t)probe_types.size() + (int64_t)build_types.size() <= kNestedLoopMaxChannels, PA_ERR_NOT_SUPPORTED, "at most 64 channels on both sides together");
+    PA_REQUIRE((int64_t)probe_types.size() + (int64_t)build_types.size() <= PA_NL_MAX_CHANNELS, PA_ERR_NOT_SUPPORTED, "at most 64 channels on both sides together");
     if (d->filter) {
         // an expression the generator does not take is refused here, not at the first page: no refusal depends on the layout signature
         std::vector<ChannelLayout> dry(plan.types.size());
@@ -547,7 +535,7 @@ private:
             return (int32_t)total;
         }
         const HeldRows& build = pages_->rows;
-        NlArgs a;
+        PaNlArgs a;
         memset(&a, 0, sizeof a);
         std::vector<ChannelLayout> layout(plan_.types.size());
         std::string sig;

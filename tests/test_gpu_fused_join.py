@@ -226,8 +226,8 @@ def test_refused_shapes(gpu):
 
 
 # ---- FilterAndProject -> LookupJoin behind one handle (pa_fused_join_create) ------------------------------------------------
-def joined_rows_oracle(oracle, probe, build, build_out, probe_out, flt=FILTER):
-    j = oracle.HashJoin(BUILD_TYPES, [0], build_out)
+def joined_rows_oracle(oracle, probe, build, build_out, probe_out, flt=FILTER, build_types=BUILD_TYPES):
+    j = oracle.HashJoin(build_types, [0], build_out)
     for p in build:
         j.add_build_page(p)
     j.build()
@@ -240,10 +240,10 @@ def joined_rows_oracle(oracle, probe, build, build_out, probe_out, flt=FILTER):
     return rows
 
 
-def joined_rows_device(probe, build, build_out, probe_out, flt=FILTER, output_mem=abi.MEM_HOST):
+def joined_rows_device(probe, build, build_out, probe_out, flt=FILTER, output_mem=abi.MEM_HOST, build_types=BUILD_TYPES):
     from presto_amd.operators import FusedJoinOperator, download_page
     bridge = LookupSourceFactory()
-    builder = HashBuilderOperator(bridge, BUILD_TYPES, [0], build_out)
+    builder = HashBuilderOperator(bridge, build_types, [0], build_out)
     op = FusedJoinOperator(bridge, PROBE_TYPES, flt, PROJECTIONS, [0], probe_out, output_mem=output_mem)
     assert not op.needsInput() and op.isBlocked()
     Driver(build, [builder]).run()
@@ -275,6 +275,21 @@ def test_fused_join_rows_and_order(gpu, oracle, n, duplicates, null_keys):
         expected = joined_rows_oracle(oracle, probe, build, build_out, probe_out)
         assert joined_rows_device(probe, build, build_out, probe_out) == expected
     assert joined_rows_device(probe, build, [1, 3], [0, 2], output_mem=abi.MEM_DEVICE) == joined_rows_oracle(oracle, probe, build, [1, 3], [0, 2])
+    if n == 1000:
+        # a nullable REAL build column carried by the probe: 1000 build rows; 4099 probe rows per page, so that both the 4-rows-per-lane
+        # path and the scalar tail run.  Bit-exact: the values (among them -0.0, a subnormal, the infinities) and the NULL flags
+        nb = 1000
+        bkeys = rng.integers(0, 1500, nb) if duplicates else rng.permutation(1500)[:nb]
+        real = rng.standard_normal(nb).astype(np.float32)
+        real[:5] = np.array([-0.0, 1e-45, np.inf, -np.inf, 3.4028235e38], dtype=np.float32)
+        rbuild = [Page([Block.bigint(bkeys, rng.random(nb) < 0.02 if null_keys else None), Block.real(real, rng.random(nb) < 0.2),
+                        Block.integer(rng.integers(0, 3, nb))], nb)]
+        rtypes = [abi.BIGINT, abi.REAL, abi.INTEGER]
+        rprobe = probe_pages(rng, 2, 4099, 1500)
+        bits = lambda rows: [r[:2] + (None if r[2] is None else int(np.float32(r[2]).view(np.uint32)),) + r[3:] for r in rows]
+        got = joined_rows_device(rprobe, rbuild, [1, 2], [0, 1], build_types=rtypes)
+        expected = joined_rows_oracle(oracle, rprobe, rbuild, [1, 2], [0, 1], build_types=rtypes)
+        assert len(expected) > 1000 and any(r[2] is None for r in expected) and bits(got) == bits(expected)
 
 
 def test_fused_join_every_row_and_no_row(gpu, oracle):

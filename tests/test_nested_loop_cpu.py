@@ -212,7 +212,7 @@ def body_of(source, kernel):
 @pytest.mark.parametrize("variant", [0, 1, 2, 3])
 def test_generated_source(variant):
     source = codegen(PT, [0, 3], BT, [3], MIXED, variant=variant)
-    source = source[source.index("struct PaNlArgs"):]     # (behind the device header)
+    source = source[source.index("#define PA_K("):]       # (behind the device header)
     lanes, nullable = variant & 1, bool(variant & 2)
     count, emit = KERNELS[lanes]
     other = KERNELS[1 - lanes]
@@ -254,10 +254,10 @@ def test_wide_build_rows_are_not_staged():
     ld = abi.decimal(30, 2)
     f = and_(*[call(abi.OP_EQUAL, abi.BOOLEAN, field(c, ld), field(c, ld)) for c in range(4)])
     source = codegen([abi.BIGINT], [0], [ld] * 4, [0], f, variant=0)
-    assert "__shared__" not in source[source.index("struct PaNlArgs"):]
+    assert "__shared__" not in source[source.index("#define PA_K("):]
     assert codegen([abi.BIGINT], [0], [ld] * 4, [0], f, variant=0, compile=True) > 0
     narrow = codegen([abi.BIGINT], [0], [ld] * 2, [0], and_(*[call(abi.OP_EQUAL, abi.BOOLEAN, field(c, ld), field(c, ld)) for c in range(2)]), variant=0)
-    assert "__shared__" in narrow[narrow.index("struct PaNlArgs"):]
+    assert "__shared__" in narrow[narrow.index("#define PA_K("):]
 
 
 def test_sources_and_build_list():
