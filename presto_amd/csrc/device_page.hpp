@@ -124,6 +124,15 @@ inline void view_column(OutColumn& o, const DevColumn& src)
 void publish_output(std::vector<OutColumn>& cols, int32_t n, int32_t mem, hipStream_t stream, pa_page* out,
                     std::vector<pa_column>& storage);
 
+// ends[0], ends[1] = the first and the last of the m + 1 offsets of a VARCHAR block on the device (its bytes are [ends[0], ends[1]) of
+// its values): two 4-byte copies and one stream sync
+inline void read_offset_ends(const int32_t* offsets, int64_t m, int32_t ends[2], hipStream_t s)
+{
+    PA_HIP(hipMemcpyAsync(&ends[0], offsets, 4, hipMemcpyDeviceToHost, s));
+    PA_HIP(hipMemcpyAsync(&ends[1], offsets + m, 4, hipMemcpyDeviceToHost, s));
+    PA_HIP(hipStreamSynchronize(s));
+}
+
 // static kernels used by staging (static_kernels.hip)
 void launch_gather_flat(const void* src, int elem_bytes, const int32_t* positions, int64_t count, void* dst, hipStream_t s);
 void launch_gather_nulls(const uint8_t* src, const int32_t* positions, int64_t count, uint8_t* dst, hipStream_t s);

@@ -50,7 +50,7 @@ Spec make_spec(const pa_filter_project_desc& fp, const pa_hash_aggregation_desc&
         auto build_proj = [&](int col) {
             auto it = proj_of_build_col.find(col);
             if (it != proj_of_build_col.end()) return it->second;
-            const int32_t t = ls.cols[col].type;
+            const int32_t t = ls.rows.cols[col].type;
             // refused here, when the operator is created, so that such a join-aggregation runs as the chain (a REAL build column has a
             // load, but no aggregation tier was ever run over one)
             PA_REQUIRE(t == PA_BIGINT || t == PA_INTEGER || t == PA_DATE || t == PA_DOUBLE || t == PA_BOOLEAN, PA_ERR_NOT_SUPPORTED,

@@ -1,16 +1,25 @@
-// held_rows.hpp -- HeldRows: every row of an operator's input so far, column by column on the device (the reference's PagesIndex:
-// flat arrays, address == position).  OrderBy (op_order_by.cpp), Window (op_window.cpp) and TopNRanking (op_topn_ranking.cpp) collect
-// their input in one, sort a permutation over its views, and read it back out by position.
+// held_rows.hpp -- HeldRows: rows collected page by page, column by column on the device (the reference's PagesIndex: flat arrays,
+// address == position).  One append for every operator that accumulates rows:
+//   OrderBy (op_order_by.cpp), Window (op_window.cpp), TopNRanking (op_topn_ranking.cpp)   their input, sorted through a permutation
+//   HashBuilder (op_join.cpp)               the build rows of a lookup source (LookupSourceImpl::rows, join_source.hpp)
+//   LookupJoin, NestedLoopJoin              a probe page that comes out over several calls and must outlive its producer's next one
+//   FilterAndProject (op_filter_project.cpp) the MergePages buffer
 //
 //   append_page / append_positions    PagesIndex.addPage: a staged page (or its rows at `positions`) behind the rows held
+//   append_column                     one column of a page whose VARCHAR ends the caller knows already (the caller counts the rows)
 //   keep_positions                    the rows at `rowids` into fresh columns (a prune)
 //   gather_sorted                     PagesIndex.appendTo: channels through a permutation into output columns
+//   reset                             no rows held, the allocations kept
+// The rules that live here and nowhere else: the first page with NULLs allocates a column's flags and clears the rows held before it;
+// VARCHAR offsets are rebased onto the bytes used; a VARCHAR column of more than INT32_MAX bytes is refused.
 // Host cost per VARCHAR channel and call: one read-back of 4 bytes (append_page: two 4-byte copies), one stream sync; a fixed-width
 // channel costs none.  The gathers by position are PositionGather's (position_gather.hpp).  Nothing here waits at the end of a call: the callers keep their own.  The row-count limit of a
 // sort stays with the operators (they word it differently, and TopNRanking prunes before it gives up).
 #pragma once
 
+#include <algorithm>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "device_page.hpp"
@@ -42,25 +51,37 @@ struct HeldRows {
         for (size_t c = 0; c < cols.size(); c++) {
             if (!held[c]) continue;
             const DevColumn& src = in.cols[c];
-            OutColumn& h = cols[c];
-            PA_REQUIRE(src.type == h.type, PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared input type");
-            if (h.varwidth) {
-                int32_t ends[2];
-                PA_HIP(hipMemcpyAsync(&ends[0], src.offsets, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipMemcpyAsync(&ends[1], src.offsets + m, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                const int64_t add = ends[1] - ends[0];
-                char* v = append_offsets(c, src.offsets, m, add, s);
-                if (add) PA_HIP(hipMemcpyAsync(v, static_cast<const char*>(src.values) + ends[0], (size_t)add, hipMemcpyDeviceToDevice, s));
-            }
-            else {
-                const size_t w = (size_t)type_width(h.type);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(rows + m) * w, (size_t)rows * w, s));
-                PA_HIP(hipMemcpyAsync(v + (size_t)rows * w, src.values, (size_t)m * w, hipMemcpyDeviceToDevice, s));
-            }
-            if (uint8_t* nl = append_nulls(h, src.nulls != nullptr, m, s)) PA_HIP(hipMemcpyAsync(nl, src.nulls, (size_t)m, hipMemcpyDeviceToDevice, s));
+            PA_REQUIRE(src.type == cols[c].type, PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared input type");
+            int32_t ends[2] = {0, 0};
+            if (cols[c].varwidth) read_offset_ends(src.offsets, m, ends, s);
+            append_column(c, src, m, ends[0], (int64_t)ends[1] - ends[0], s);
         }
         rows += m;
+    }
+
+    // the m rows of one column behind the rows held; a VARCHAR's bytes are [first, first + add) of src.values.  `rows` is the caller's
+    // to advance, once every column of the page is in.
+    void append_column(size_t c, const DevColumn& src, int64_t m, int32_t first, int64_t add, hipStream_t s)
+    {
+        OutColumn& h = cols[c];
+        if (h.varwidth) {
+            char* v = append_offsets(c, src.offsets, m, add, s);
+            if (add) PA_HIP(hipMemcpyAsync(v, static_cast<const char*>(src.values) + first, (size_t)add, hipMemcpyDeviceToDevice, s));
+        }
+        else {
+            const size_t w = (size_t)type_width(h.type);
+            char* v = static_cast<char*>(h.values.reserve_keep((size_t)room(m) * w, (size_t)rows * w, s));
+            PA_HIP(hipMemcpyAsync(v + (size_t)rows * w, src.values, (size_t)m * w, hipMemcpyDeviceToDevice, s));
+        }
+        if (uint8_t* nl = append_nulls(h, src.nulls != nullptr, m, s)) PA_HIP(hipMemcpyAsync(nl, src.nulls, (size_t)m, hipMemcpyDeviceToDevice, s));
+    }
+
+    // no rows held; the allocations stay
+    void reset()
+    {
+        rows = 0;
+        std::fill(var_bytes.begin(), var_bytes.end(), 0);
+        for (OutColumn& o : cols) o.has_nulls = false;
     }
 
     // Block.copyPositions: the k rows of a staged page at `positions` behind the rows held (varchar_tmp: the caller's scratch column)
@@ -78,7 +99,7 @@ struct HeldRows {
             }
             else {
                 const size_t w = (size_t)type_width(h.type);
-                char* v = static_cast<char*>(h.values.reserve_keep((size_t)(rows + k) * w, (size_t)rows * w, s));
+                char* v = static_cast<char*>(h.values.reserve_keep((size_t)room(k) * w, (size_t)rows * w, s));
                 launch_gather_flat(src.values, (int)w, positions, k, v + (size_t)rows * w, s);
             }
             if (uint8_t* nl = append_nulls(h, src.nulls != nullptr, k, s)) launch_gather_nulls(src.nulls, positions, k, nl, s);
@@ -165,15 +186,18 @@ struct HeldRows {
     std::vector<int64_t> var_bytes;   // VARCHAR bytes used
     std::vector<bool> held;
     int64_t rows = 0;
+    int64_t reserve_rows = 0;          // room for at least this many rows whenever a column grows (HashBuilder's expected_positions)
+    const char* refusal_prefix = "";   // in front of "VARCHAR column exceeds 2 GB" (the join build says whose column)
 
 private:
+    int64_t room(int64_t k) const { return std::max(rows + k, reserve_rows); }
     // k offsets (src[0..k], any base) behind the rows held, rebased onto the `add` bytes they bring; returns where those bytes go
     char* append_offsets(size_t c, const int32_t* src, int64_t k, int64_t add, hipStream_t s)
     {
         OutColumn& h = cols[c];
         int64_t& used = var_bytes[c];
-        PA_REQUIRE(add >= 0 && used + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "VARCHAR column exceeds 2 GB");
-        int32_t* off = static_cast<int32_t*>(h.offsets.reserve_keep((size_t)(rows + k + 1) * 4, (size_t)(rows ? rows + 1 : 0) * 4, s));
+        PA_REQUIRE(add >= 0 && used + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, std::string(refusal_prefix) + "VARCHAR column exceeds 2 GB");
+        int32_t* off = static_cast<int32_t*>(h.offsets.reserve_keep((size_t)(room(k) + 1) * 4, (size_t)(rows ? rows + 1 : 0) * 4, s));
         launch_offsets_append(src, k, (int32_t)used, off + rows, rows == 0, s);
         char* v = static_cast<char*>(h.values.reserve_keep((size_t)(used + add + 1), (size_t)used, s)) + used;
         used += add;
@@ -184,7 +208,7 @@ private:
     uint8_t* append_nulls(OutColumn& h, bool src_has_nulls, int64_t k, hipStream_t s)
     {
         if (!src_has_nulls && !h.has_nulls) return nullptr;
-        uint8_t* nl = static_cast<uint8_t*>(h.nulls.reserve_keep((size_t)(rows + k), h.has_nulls ? (size_t)rows : 0, s));
+        uint8_t* nl = static_cast<uint8_t*>(h.nulls.reserve_keep((size_t)room(k), h.has_nulls ? (size_t)rows : 0, s));
         if (!h.has_nulls && rows > 0) PA_HIP(hipMemsetAsync(nl, 0, (size_t)rows, s));
         h.has_nulls = true;
         if (src_has_nulls) return nl + rows;

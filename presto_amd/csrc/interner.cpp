@@ -82,6 +82,7 @@ const int32_t* StringInterner::intern(const void* values, const int32_t* offsets
         int64_t bytes = bytes_hint;
         if (bytes < 0) {
             int32_t* hb = reinterpret_cast<int32_t*>(h + 4);
+            // (a slice's two ends, as read_offset_ends reads them -- spelled out here because they land in this interner's pinned words)
             PA_HIP(hipMemcpyAsync(hb, offsets + at, 4, hipMemcpyDeviceToHost, s));
             PA_HIP(hipMemcpyAsync(hb + 1, offsets + at + rows, 4, hipMemcpyDeviceToHost, s));
             PA_HIP(hipStreamSynchronize(s));

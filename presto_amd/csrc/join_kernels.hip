@@ -128,17 +128,6 @@ void launch_fill_i32(int32_t* dst, int32_t value, int64_t n, hipStream_t s)
     PA_HIP(hipGetLastError());
 }
 
-__global__ __launch_bounds__(256) void k_rebase_offsets(const i32* __restrict__ in, i32 in_base, i32 out_base, i64 n, i32* __restrict__ out)
-{
-    for (i64 i = (i64)blockIdx.x * 256 + threadIdx.x; i < n; i += (i64)gridDim.x * 256) out[i] = in[i] - in_base + out_base;
-}
-void launch_rebase_offsets(const int32_t* in, int32_t in_base, int32_t out_base, int64_t n_plus_1, int32_t* out, hipStream_t s)
-{
-    if (n_plus_1 <= 0) return;
-    hipLaunchKernelGGL(k_rebase_offsets, grid_for(n_plus_1), 256, 0, s, in, in_base, out_base, (i64)n_plus_1, out);
-    PA_HIP(hipGetLastError());
-}
-
 // the types jcol_equal has a case for (the probe kernel carries no error word: both launches that compare keys ask here first)
 static void require_equal_types(const JoinKeys& k)
 {

@@ -137,7 +137,6 @@ void launch_join_unvisited_flag(const uint8_t* visited, int64_t n, int32_t* part
 void launch_join_probe_emit(const int32_t* head, const int32_t* offsets, int32_t n_probe, int32_t total, const int32_t* links, int32_t* probe_idx,
                             int32_t* build_pos, int flags, uint8_t* visited, hipStream_t s);
 void launch_fill_i32(int32_t* dst, int32_t value, int64_t n, hipStream_t s);
-void launch_rebase_offsets(const int32_t* in, int32_t in_base, int32_t out_base, int64_t n_plus_1, int32_t* out, hipStream_t s);
 
 // JoinFilterFunction: from the indices of the candidates the filter kept (`eligible`, ascending = emission order) to output pairs
 void launch_jf_first_of_row(const int32_t* eligible, int32_t ne, const int32_t* cand_probe, int32_t* keep, hipStream_t s);

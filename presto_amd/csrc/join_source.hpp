@@ -13,27 +13,10 @@
 
 #include "common.hpp"
 #include "device_page.hpp"
+#include "held_rows.hpp"
 #include "join_kernels.hpp"
 
 namespace pa {
-
-struct BuildColumn {
-    int32_t type = PA_BIGINT;
-    bool varwidth = false;
-    DevBuf values, offsets, nulls;
-    bool has_nulls = false;
-    int64_t bytes = 0;  // VARWIDTH: bytes used
-    DevColumn view() const
-    {
-        DevColumn c;
-        c.type = type;
-        c.varwidth = varwidth;
-        c.values = values.ptr();
-        c.offsets = offsets.as<int32_t>();
-        c.nulls = has_nulls ? nulls.as<uint8_t>() : nullptr;
-        return c;
-    }
-};
 
 // The lookup source shared between the build operator and its probe operators
 // (LookupSourceFactory / JoinBridge; PartitionedLookupSourceFactory.java:179-206).
@@ -49,8 +32,13 @@ struct LookupSourceImpl {
     {
         for (const Release& r : releases) r.fn(r.ctx);
     }
-    std::vector<BuildColumn> cols;
-    int32_t n = 0;
+    HeldRows rows;   // every channel of the build pages, by build channel (PagesIndex.addPage)
+    int32_t n() const { return (int32_t)rows.rows; }   // (HashBuilder keeps the build side under 2^31 positions)
+    void init_rows(const int32_t* types, int32_t channels)
+    {
+        rows.init(std::vector<int32_t>(types, types + channels), std::vector<bool>((size_t)channels, true));
+        rows.refusal_prefix = "build ";
+    }
     std::vector<int> join_channels, output_channels;
     int hash_channel = -1;
     DevBuf key, links, raw_hash, slot_of, tagged;
@@ -75,7 +63,7 @@ struct LookupSourceImpl {
     uint8_t* visited_positions(hipStream_t s)
     {
         std::call_once(visited_once, [&] {
-            const size_t bytes = (size_t)std::max(n, 1);
+            const size_t bytes = (size_t)std::max(n(), 1);
             PA_HIP(hipMemsetAsync(visited.ensure(bytes), 0, bytes, s));
             PA_HIP(hipStreamSynchronize(s));  // (probe operators on other streams may be the next to touch it)
         });
@@ -93,10 +81,10 @@ struct LookupSourceImpl {
         memset(&k, 0, sizeof k);
         k.ncols = (int32_t)join_channels.size();
         for (int i = 0; i < k.ncols; i++) {
-            const BuildColumn& c = cols[join_channels[i]];
-            k.col[i].values = c.values.ptr();
-            k.col[i].offsets = c.offsets.as<int32_t>();
-            k.col[i].nulls = c.has_nulls ? c.nulls.as<uint8_t>() : nullptr;
+            const DevColumn c = rows.view(join_channels[i]);
+            k.col[i].values = c.values;
+            k.col[i].offsets = c.offsets;
+            k.col[i].nulls = c.nulls;
             k.col[i].type = c.type;
         }
         return k;

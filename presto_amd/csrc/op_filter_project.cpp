@@ -23,6 +23,7 @@
 #include <sstream>
 
 #include "exprgen.hpp"
+#include "held_rows.hpp"
 #include "jit.hpp"
 #include "operator.hpp"
 #include "position_gather.hpp"
@@ -470,7 +471,7 @@ public:
             if (have) {
                 const int64_t bytes = page_size_in_bytes(count);
                 if (count >= merge_min_rows_ || bytes >= merge_min_bytes_) {  // :128
-                    if (m_rows_ == 0) {
+                    if (merged_.rows == 0) {
                         publish_output(out_cols_, count, spec_.output_mem, s, out, out_storage_);
                         return true;
                     }
@@ -482,7 +483,7 @@ public:
                 if (m_size_ >= merge_max_bytes_) return flush_merged(out);  // :143-145
             }
         }
-        if (finishing_ && m_rows_ > 0) return flush_merged(out);  // :121-124
+        if (finishing_ && merged_.rows > 0) return flush_merged(out);  // :121-124
         return false;
     }
 
@@ -563,9 +564,7 @@ public:
             }
             const int32_t* off = oc.is_view ? oc.view_offsets : oc.offsets.as<int32_t>();
             int32_t ends[2];
-            PA_HIP(hipMemcpyAsync(&ends[0], off, 4, hipMemcpyDeviceToHost, s));
-            PA_HIP(hipMemcpyAsync(&ends[1], off + count, 4, hipMemcpyDeviceToHost, s));
-            PA_HIP(hipStreamSynchronize(s));
+            read_offset_ends(off, count, ends, s);
             var_first_[j] = ends[0];
             var_bytes_[j] = ends[1] - ends[0];
             bytes += (int64_t)var_bytes_[j] + 5LL * count;
@@ -577,62 +576,36 @@ public:
     void append_merged(int32_t count, int64_t bytes)
     {
         hipStream_t s = stream_.get();
-        if (merge_cols_.size() != out_cols_.size()) {
-            merge_cols_.clear();
-            merge_cols_.resize(out_cols_.size());
-            m_var_bytes_.assign(out_cols_.size(), 0);
+        if (merged_.cols.empty()) {
+            std::vector<int32_t> types;
+            for (const OutColumn& oc : out_cols_) types.push_back(oc.type);
+            merged_.init(types, std::vector<bool>(types.size(), true));
         }
         for (size_t j = 0; j < out_cols_.size(); j++) {
-            OutColumn& oc = out_cols_[j];
-            OutColumn& mc = merge_cols_[j];
-            const void* sv = oc.is_view ? oc.view_values : oc.values.ptr();
-            const uint8_t* sn = oc.is_view ? oc.view_nulls : (oc.has_nulls ? oc.nulls.as<uint8_t>() : nullptr);
-            mc.type = oc.type;
-            mc.varwidth = oc.varwidth;
-            if (oc.varwidth) {
-                const int32_t* so = oc.is_view ? oc.view_offsets : oc.offsets.as<int32_t>();
-                int32_t* mo = static_cast<int32_t*>(mc.offsets.reserve_keep((size_t)(m_rows_ + count + 1) * 4, (size_t)(m_rows_ ? m_rows_ + 1 : 0) * 4, s));
-                launch_offsets_append(so, count, (int32_t)m_var_bytes_[j], mo + m_rows_, m_rows_ == 0, s);
-                char* mv = static_cast<char*>(mc.values.reserve_keep((size_t)(m_var_bytes_[j] + var_bytes_[j] + 1), (size_t)m_var_bytes_[j], s));
-                if (var_bytes_[j] > 0)
-                    PA_HIP(hipMemcpyAsync(mv + m_var_bytes_[j], static_cast<const char*>(sv) + var_first_[j], (size_t)var_bytes_[j], hipMemcpyDeviceToDevice, s));
-                m_var_bytes_[j] += var_bytes_[j];
-            }
-            else {
-                const size_t w = (size_t)type_width(oc.type);
-                char* mv = static_cast<char*>(mc.values.reserve_keep((size_t)(m_rows_ + count) * w, (size_t)m_rows_ * w, s));
-                PA_HIP(hipMemcpyAsync(mv + (size_t)m_rows_ * w, sv, (size_t)count * w, hipMemcpyDeviceToDevice, s));
-            }
-            if (sn || mc.has_nulls) {
-                uint8_t* mn = static_cast<uint8_t*>(mc.nulls.reserve_keep((size_t)(m_rows_ + count), mc.has_nulls ? (size_t)m_rows_ : 0, s));
-                if (!mc.has_nulls && m_rows_ > 0) PA_HIP(hipMemsetAsync(mn, 0, (size_t)m_rows_, s));  // earlier pages had no NULL
-                if (sn) PA_HIP(hipMemcpyAsync(mn + m_rows_, sn, (size_t)count, hipMemcpyDeviceToDevice, s));
-                else PA_HIP(hipMemsetAsync(mn + m_rows_, 0, (size_t)count, s));
-                mc.has_nulls = true;
-            }
+            const OutColumn& oc = out_cols_[j];
+            DevColumn src;
+            src.type = oc.type;
+            src.varwidth = oc.varwidth;
+            src.values = oc.is_view ? oc.view_values : oc.values.ptr();
+            src.offsets = oc.is_view ? oc.view_offsets : oc.offsets.as<int32_t>();
+            src.nulls = oc.is_view ? oc.view_nulls : (oc.has_nulls ? oc.nulls.as<uint8_t>() : nullptr);
+            merged_.append_column(j, src, count, var_first_[j], var_bytes_[j], s);   // (the ends page_size_in_bytes has read)
         }
-        m_rows_ += count;
+        merged_.rows += count;
         m_size_ += bytes;
     }
 
     // pageBuilder.build() + reset(): the buffered rows leave as one page (valid until the next add_input / get_output)
     bool flush_merged(pa_page* out)
     {
-        const int32_t n = (int32_t)m_rows_;
-        for (auto& mc : merge_cols_) {
-            mc.is_view = false;
-            mc.host_ready = false;
-        }
-        publish_output(merge_cols_, n, spec_.output_mem, stream_.get(), out, merge_storage_);
-        m_rows_ = 0;
+        publish_output(merged_.cols, (int32_t)merged_.rows, spec_.output_mem, stream_.get(), out, merge_storage_);
+        merged_.reset();   // (the pointers of the published page are already taken)
         m_size_ = 0;
-        for (auto& mc : merge_cols_) mc.has_nulls = false;  // the pointers of the published page are already taken
-        std::fill(m_var_bytes_.begin(), m_var_bytes_.end(), 0);
         return true;
     }
 
     void finish() override { finishing_ = true; }
-    bool is_finished() override { return finishing_ && !pending_ && !big_queued_ && m_rows_ == 0; }
+    bool is_finished() override { return finishing_ && !pending_ && !big_queued_ && merged_.rows == 0; }
     int64_t memory_bytes() override { return (int64_t)(stager_.bytes() + sel4_.capacity() + positions_.capacity() + tile_counts_.capacity()); }
 
     // SelectedPositions of the last processed page (after its get_output)
@@ -839,10 +812,9 @@ private:
     // MergePages state
     bool merging_ = false, big_queued_ = false;
     int32_t merge_min_rows_ = 0, big_count_ = 0;
-    int64_t merge_min_bytes_ = 0, merge_max_bytes_ = 1 << 20, m_rows_ = 0, m_size_ = 0;
-    std::vector<OutColumn> merge_cols_;
+    int64_t merge_min_bytes_ = 0, merge_max_bytes_ = 1 << 20, m_size_ = 0;
+    HeldRows merged_;   // the buffered rows (PageBuilder)
     std::vector<pa_column> merge_storage_;
-    std::vector<int64_t> m_var_bytes_;
     std::vector<int32_t> var_first_, var_bytes_;
 };
 

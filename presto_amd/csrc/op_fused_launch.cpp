@@ -113,7 +113,7 @@ bool FusedAggregationOperator::run_page_build_rows(const Compiled& ck, const Dev
     HostTraceScope trace("    fused.run_page_build_rows");
     hipStream_t s = stream_.get();
     const KernelInfo& ki = ck.info;
-    const uint32_t slots = (uint32_t)std::max(spec_.join->ls->n, 1);
+    const uint32_t slots = (uint32_t)std::max(spec_.join->ls->n(), 1);
     if (gt_.cap == 0) {
         brow_occ_word_ = ki.occ_word;
         brow_occ_empty_ = ki.occ_empty;
@@ -196,7 +196,7 @@ bool FusedAggregationOperator::run_page(const Compiled& ck, const DevPage& dp, b
     a.overflow_rows = reinterpret_cast<uint64_t*>(ctl_ + 2);
     if (spec_.join) {
         fill_probe_args(a, *spec_.join);
-        a.jrows = spec_.join->ls->n;
+        a.jrows = spec_.join->ls->n();
     }
     if (ki.variant == V_BROW) return run_page_build_rows(ck, dp, a, start_row);
     // a table of ranges: one launch takes all of them, a workgroup per entry at a time

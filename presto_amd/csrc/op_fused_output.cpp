@@ -51,12 +51,12 @@ bool FusedAggregationOperator::emit_on_device(const KernelInfo& ki, int64_t grou
             const OwnedExpr& pe = spec_.proj[(size_t)spec_.join->brow_group_proj[(size_t)gi]];
             const int v = pe.is_input_ref() ? pe.node(pe.root).channel - spec_.n_in : -1;
             if (v < 0 || v >= (int)spec_.join->build_cols.size()) return false;
-            const BuildColumn& bc = spec_.join->ls->cols[(size_t)spec_.join->build_cols[(size_t)v]];
+            const DevColumn bc = spec_.join->ls->rows.view(spec_.join->build_cols[(size_t)v]);
             GtEmitCol* c = add(GT_EMIT_COLUMN, kp.type);
             if (!c || bc.varwidth || type_width(bc.type) != c->width) return false;
-            c->src = bc.values.ptr();
-            c->src_nulls = bc.has_nulls ? bc.nulls.as<uint8_t>() : nullptr;
-            nullable.push_back(bc.has_nulls);
+            c->src = bc.values;
+            c->src_nulls = bc.nulls;
+            nullable.push_back(bc.nulls != nullptr);
             continue;
         }
         GtEmitCol* c = add(GT_EMIT_KEY, kp.type);
@@ -281,7 +281,7 @@ bool FusedAggregationOperator::fetch_result(const KernelInfo& ki, std::vector<ui
             PaFusedArgs a;
             memset(&a, 0, sizeof a);
             fill_probe_args(a, *spec_.join);
-            a.jrows = spec_.join->ls->n;
+            a.jrows = spec_.join->ls->n();
             a.err = ctl_;
             a.gt_count = ctl_ + 1;
             PA_HIP(hipMemsetAsync(ctl_ + 1, 0, 4, s));

@@ -35,7 +35,7 @@ void fill_raw_hash(LookupSourceImpl& ls, const JoinKeys& bk, int32_t n, hipStrea
     ls.raw_hash.ensure((size_t)std::max(n, 1) * 8);
     if (n <= 0) return;
     if (ls.hash_channel >= 0) {
-        PA_HIP(hipMemcpyAsync(ls.raw_hash.ptr(), ls.cols[ls.hash_channel].values.ptr(), (size_t)n * 8, hipMemcpyDeviceToDevice, s));
+        PA_HIP(hipMemcpyAsync(ls.raw_hash.ptr(), ls.rows.cols[ls.hash_channel].values.ptr(), (size_t)n * 8, hipMemcpyDeviceToDevice, s));
         return;
     }
     HashPageArgs ha;
@@ -73,11 +73,7 @@ public:
         PA_REQUIRE(d->input_channel_count > 0 && d->input_channel_count <= 32, PA_ERR_NOT_SUPPORTED, "1..32 build channels");
         PA_REQUIRE(d->join_channel_count > 0 && d->join_channel_count <= kMaxJoinChannels, PA_ERR_NOT_SUPPORTED, "1..8 join channels");
         ls_ = std::make_shared<LookupSourceImpl>();
-        ls_->cols.resize(d->input_channel_count);
-        for (int c = 0; c < d->input_channel_count; c++) {
-            ls_->cols[c].type = d->input_types[c];
-            ls_->cols[c].varwidth = d->input_types[c] == PA_VARCHAR;
-        }
+        ls_->init_rows(d->input_types, d->input_channel_count);
         for (int i = 0; i < d->join_channel_count; i++) {
             PA_REQUIRE(d->join_channels[i] >= 0 && d->join_channels[i] < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "join channel out of range");
             ls_->join_channels.push_back(d->join_channels[i]);
@@ -93,7 +89,7 @@ public:
         ls_->hash_channel = d->hash_channel;
         PA_REQUIRE(ls_->hash_channel < d->input_channel_count, PA_ERR_INVALID_ARGUMENT, "hash channel out of range");
         PA_REQUIRE(ls_->hash_channel < 0 || d->input_types[ls_->hash_channel] == PA_BIGINT, PA_ERR_INVALID_ARGUMENT, "hash channel must be BIGINT");
-        expected_ = d->expected_positions;
+        ls_->rows.reserve_rows = d->expected_positions;   // (room for that many rows from the first page on)
         bridge->impl = ls_;
         ctl_ = static_cast<int32_t*>(ctl_buf_.ensure(64));
         PA_HIP(hipMemsetAsync(ctl_, 0, 64, stream_.get()));
@@ -108,7 +104,8 @@ public:
     {
         PA_REQUIRE(!finishing_, PA_ERR_ILLEGAL_STATE, "Operator is already finishing");
         PA_REQUIRE(page != nullptr, PA_ERR_INVALID_ARGUMENT, "page is null");
-        PA_REQUIRE(page->channel_count == (int32_t)ls_->cols.size(), PA_ERR_INVALID_ARGUMENT, "page channel count does not match the build types");
+        const std::vector<OutColumn>& cols = ls_->rows.cols;
+        PA_REQUIRE(page->channel_count == (int32_t)cols.size(), PA_ERR_INVALID_ARGUMENT, "page channel count does not match the build types");
         const int64_t m = page->position_count;
         const bool retained = (page->flags & PA_PAGE_RETAINED) != 0 && page->release != nullptr;
         if (m == 0) {
@@ -118,7 +115,7 @@ public:
         // The first page of a build side, kept alive by its owner (PA_PAGE_RETAINED): PagesIndex would hold on to the Page's blocks --
         // so do the build columns: the flat block arrays are read in place until the lookup source is destroyed (a second page
         // moves them into allocations of their own, reserve_keep).  A build side that arrives as one page is never copied.
-        if (retained && ls_->n == 0 && page->mem == PA_MEM_DEVICE && borrow_page(page)) return;
+        if (retained && ls_->n() == 0 && page->mem == PA_MEM_DEVICE && borrow_page(page)) return;
         // (a retained page that is copied after all goes back to its owner when the copies have run -- also when a check below throws)
         struct ReleaseAtExit {
             const pa_page* p;
@@ -131,42 +128,11 @@ public:
                 p->release(p->release_ctx);
             }
         } release_at_exit{page, retained, stream_.get()};
-        PA_REQUIRE((int64_t)ls_->n + m <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "build side exceeds 2^31 positions");
+        PA_REQUIRE((int64_t)ls_->n() + m <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "build side exceeds 2^31 positions");
         hipStream_t s = stream_.get();
         DevPage dp = stager_.stage(page, nullptr, s);
-        const int64_t n0 = ls_->n;
-        const int64_t want = std::max<int64_t>(n0 + m, expected_);
-        for (size_t c = 0; c < ls_->cols.size(); c++) {
-            BuildColumn& bc = ls_->cols[c];
-            const DevColumn& in = dp.cols[c];
-            PA_REQUIRE(in.type == bc.type, PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared build type");
-            if (bc.varwidth) {
-                int32_t ends[2] = {0, 0};
-                PA_HIP(hipMemcpyAsync(&ends[0], in.offsets, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipMemcpyAsync(&ends[1], in.offsets + m, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                int64_t add = (int64_t)ends[1] - ends[0];
-                PA_REQUIRE(bc.bytes + add <= INT32_MAX, PA_ERR_INSUFFICIENT_RESOURCES, "build VARCHAR column exceeds 2 GB");
-                bc.offsets.reserve_keep((size_t)(want + 1) * 4, (size_t)(n0 + 1) * 4, s);
-                bc.values.reserve_keep((size_t)std::max<int64_t>(bc.bytes + add, 16), (size_t)bc.bytes, s);
-                launch_rebase_offsets(in.offsets, ends[0], (int32_t)bc.bytes, m + 1, bc.offsets.as<int32_t>() + n0, s);
-                if (add) PA_HIP(hipMemcpyAsync(bc.values.as<char>() + bc.bytes, static_cast<const char*>(in.values) + ends[0], (size_t)add, hipMemcpyDeviceToDevice, s));
-                bc.bytes += add;
-            }
-            else {
-                int w = type_width(bc.type);
-                bc.values.reserve_keep((size_t)want * w, (size_t)n0 * w, s);
-                PA_HIP(hipMemcpyAsync(bc.values.as<char>() + n0 * w, in.values, (size_t)m * w, hipMemcpyDeviceToDevice, s));
-            }
-            if (in.nulls || bc.has_nulls) {
-                bc.nulls.reserve_keep((size_t)want, bc.has_nulls ? (size_t)n0 : 0, s);
-                if (!bc.has_nulls && n0) PA_HIP(hipMemsetAsync(bc.nulls.ptr(), 0, (size_t)n0, s));
-                if (in.nulls) PA_HIP(hipMemcpyAsync(bc.nulls.as<char>() + n0, in.nulls, (size_t)m, hipMemcpyDeviceToDevice, s));
-                else PA_HIP(hipMemsetAsync(bc.nulls.as<char>() + n0, 0, (size_t)m, s));
-                bc.has_nulls = true;
-            }
-        }
-        ls_->n = (int32_t)(n0 + m);
+        for (size_t c = 0; c < cols.size(); c++) PA_REQUIRE(dp.cols[c].type == cols[c].type, PA_ERR_INVALID_ARGUMENT, "page block type does not match the declared build type");
+        ls_->rows.append_page(dp, m, s);
         // staged host pages live in the stager's arena, which the next add_input overwrites.  (A device page is its producer's again
         // with that operator's next call: on the caller's stream these copies are ordered before it, a stream of this operator's own
         // is drained by pa_op_add_input -- abi.cpp.)  A retained page that was copied is handed back once the copies have run.
@@ -177,23 +143,24 @@ public:
     bool borrow_page(const pa_page* page)
     {
         const int64_t m = page->position_count;
-        for (size_t c = 0; c < ls_->cols.size(); c++) {
+        std::vector<OutColumn>& cols = ls_->rows.cols;
+        for (size_t c = 0; c < cols.size(); c++) {
             const pa_column& in = page->columns[c];
-            const BuildColumn& bc = ls_->cols[c];
+            const OutColumn& bc = cols[c];
             if (in.type != bc.type || in.values == nullptr) return false;
             if (bc.varwidth ? in.encoding != PA_VARWIDTH : in.encoding != PA_FLAT) return false;
             if (bc.varwidth) return false;   // (a block's offsets need not start at 0: variable-width channels are appended as before)
         }
-        for (size_t c = 0; c < ls_->cols.size(); c++) {
+        for (size_t c = 0; c < cols.size(); c++) {
             const pa_column& in = page->columns[c];
-            BuildColumn& bc = ls_->cols[c];
+            OutColumn& bc = cols[c];
             bc.values.borrow(in.values, (size_t)m * type_width(bc.type));
             if (in.nulls) {
                 bc.nulls.borrow(in.nulls, (size_t)m);
                 bc.has_nulls = true;
             }
         }
-        ls_->n = (int32_t)m;
+        ls_->rows.rows = m;
         ls_->releases.push_back(LookupSourceImpl::Release{page->release, page->release_ctx});
         return true;
     }
@@ -204,7 +171,7 @@ public:
         if (finishing_) return;
         finishing_ = true;
         hipStream_t s = stream_.get();
-        const int32_t n = ls_->n;
+        const int32_t n = ls_->n();
         const uint32_t hash_size = array_size(n);
         ls_->mask = hash_size - 1;
         ls_->links.ensure((size_t)std::max(n, 1) * 4);
@@ -283,7 +250,7 @@ public:
     int32_t build_key_slots(const JoinCol& key, int32_t n, uint64_t slots, hipStream_t s)
     {
         const int64_t* raw = nullptr;
-        if (ls_->hash_channel >= 0 && n > 0) raw = ls_->cols[ls_->hash_channel].values.as<int64_t>();
+        if (ls_->hash_channel >= 0 && n > 0) raw = ls_->rows.cols[ls_->hash_channel].values.as<int64_t>();
         JoinKeySlot* table = static_cast<JoinKeySlot*>(ls_->key_slots.ensure((size_t)slots * sizeof(JoinKeySlot)));
         ls_->probe_wrap = ls_->probe_mask;
         // large build sides: rows regrouped by the partition of their home slot, tables assembled in LDS and written once
@@ -304,7 +271,7 @@ public:
     int32_t build_key_slots_plain(const JoinCol& key, int32_t n, JoinKeySlot* table, hipStream_t s)
     {
         const int64_t* raw = nullptr;
-        if (ls_->hash_channel >= 0 && n > 0) raw = ls_->cols[ls_->hash_channel].values.as<int64_t>();
+        if (ls_->hash_channel >= 0 && n > 0) raw = ls_->rows.cols[ls_->hash_channel].values.as<int64_t>();
         links_built_ = false;
         int32_t dups = 0;
         PA_HIP(hipMemsetAsync(ctl_ + 1, 0, 8, s));
@@ -459,8 +426,7 @@ public:
     int64_t memory_bytes() override
     {
         int64_t b = (int64_t)(ls_->key.capacity() + ls_->links.capacity() + ls_->raw_hash.capacity() + ls_->slot_of.capacity() + ls_->tagged.capacity() + ls_->key_slots.capacity() + ls_->key_bits.capacity() + ls_->rank_words.capacity() + ls_->rank_rows.capacity());
-        for (const auto& c : ls_->cols) b += (int64_t)(c.values.capacity() + c.offsets.capacity() + c.nulls.capacity());
-        return b;
+        return b + (int64_t)ls_->rows.bytes();
     }
 
 private:
@@ -478,7 +444,6 @@ private:
     int32_t pairs_ = 0, pair_partitions_ = 0;
     int pair_shift_ = 0;
     int32_t* ctl_ = nullptr;
-    int64_t expected_ = 0;
     bool finishing_ = false;
 };
 
@@ -496,7 +461,7 @@ public:
         for (int i = 0; i < d->join_channel_count; i++) {
             int c = d->probe_join_channels[i];
             PA_REQUIRE(c >= 0 && c < n_probe_channels_, PA_ERR_INVALID_ARGUMENT, "probe join channel out of range");
-            PA_REQUIRE(probe_types_[c] == ls_->cols[ls_->join_channels[i]].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
+            PA_REQUIRE(probe_types_[c] == ls_->rows.cols[ls_->join_channels[i]].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
             join_channels_.push_back(c);
         }
         hash_channel_ = d->probe_hash_channel;
@@ -731,7 +696,7 @@ public:
             gather_column(src, probe_idx, total_out, out_col, s);
         }
         for (int c : ls_->output_channels) {
-            const DevColumn src = ls_->cols[c].view();
+            const DevColumn src = ls_->rows.view(c);
             OutColumn& out_col = out_cols_[oc++];
             if (!src.varwidth && flat(src.type, src.values, src.nulls, 1, probe_outer_, out_col)) continue;
             gather_column(src, build_pos, total_out, out_col, s, probe_outer_);
@@ -756,8 +721,8 @@ public:
             if (in_.cols[c].varwidth || (w != 1 && w != 4 && w != 8)) return false;
         }
         for (int c : ls_->output_channels) {
-            const int w = type_width(ls_->cols[c].type);
-            if (ls_->cols[c].varwidth || (w != 1 && w != 4 && w != 8)) return false;
+            const int w = type_width(ls_->rows.cols[c].type);
+            if (ls_->rows.cols[c].varwidth || (w != 1 && w != 4 && w != 8)) return false;
         }
         return output_channels_.size() + ls_->output_channels.size() <= (size_t)GATHER_MULTI_MAX_COLS;
     }
@@ -795,8 +760,8 @@ public:
         };
         for (int c : output_channels_) flat(in_.cols[c].type, in_.cols[c].values, in_.cols[c].nulls, 0, false, out_cols_[oc++]);
         for (int c : ls_->output_channels) {
-            const BuildColumn& src = ls_->cols[c];
-            flat(src.type, src.values.ptr(), src.has_nulls ? src.nulls.as<uint8_t>() : nullptr, 1, probe_outer_, out_cols_[oc++]);
+            const DevColumn src = ls_->rows.view(c);
+            flat(src.type, src.values, src.nulls, 1, probe_outer_, out_cols_[oc++]);
         }
         launch_gather_multi(gm, s);
         eager_ = true;
@@ -805,36 +770,14 @@ public:
     // private copies of the probe page's channels this operator reads (in_ is repointed to them)
     void keep_input(hipStream_t s)
     {
-        const int64_t n = in_.n;
-        kept_.resize(in_.cols.size() * 3);
-        for (size_t c = 0; c < in_.cols.size(); c++) {
-            if (!needed_[c]) continue;
-            DevColumn& col = in_.cols[c];
-            if (col.values == nullptr) continue;
-            if (col.varwidth) {
-                int32_t ends[2] = {0, 0};
-                PA_HIP(hipMemcpyAsync(&ends[0], col.offsets, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipMemcpyAsync(&ends[1], col.offsets + n, 4, hipMemcpyDeviceToHost, s));
-                PA_HIP(hipStreamSynchronize(s));
-                const size_t bytes = (size_t)(ends[1] - ends[0]);
-                char* v = static_cast<char*>(kept_[3 * c].ensure(bytes ? bytes : 1));
-                if (bytes) PA_HIP(hipMemcpyAsync(v, static_cast<const char*>(col.values) + ends[0], bytes, hipMemcpyDeviceToDevice, s));
-                int32_t* o = static_cast<int32_t*>(kept_[3 * c + 1].ensure((size_t)(n + 1) * 4));
-                PA_HIP(hipMemcpyAsync(o, col.offsets, (size_t)(n + 1) * 4, hipMemcpyDeviceToDevice, s));
-                col.values = v - ends[0];  // (the offsets stay absolute)
-                col.offsets = o;
-            }
-            else {
-                const size_t bytes = (size_t)n * type_width(col.type);
-                void* v = kept_[3 * c].ensure(bytes ? bytes : 1);
-                if (bytes) PA_HIP(hipMemcpyAsync(v, col.values, bytes, hipMemcpyDeviceToDevice, s));
-                col.values = v;
-            }
-            if (col.nulls) {
-                uint8_t* nl = static_cast<uint8_t*>(kept_[3 * c + 2].ensure((size_t)n));
-                PA_HIP(hipMemcpyAsync(nl, col.nulls, (size_t)n, hipMemcpyDeviceToDevice, s));
-                col.nulls = nl;
-            }
+        // (typed as this page's staged columns are: only the join channels' types are checked against the declaration)
+        std::vector<int32_t> types;
+        for (const DevColumn& c : in_.cols) types.push_back(c.type);
+        kept_.init(types, needed_);
+        kept_.reset();
+        kept_.append_page(in_, in_.n, s);
+        for (size_t c = 0; c < needed_.size(); c++) {
+            if (needed_[c]) in_.cols[c] = kept_.view((int32_t)c);
         }
         PA_HIP(hipStreamSynchronize(s));
         in_volatile_ = false;
@@ -860,12 +803,12 @@ public:
     {
         OwnedExpr e = OwnedExpr::copy(f);
         PA_REQUIRE(e.root_type() == PA_BOOLEAN, PA_ERR_INVALID_ARGUMENT, "join filter must be BOOLEAN");
-        const int nb = (int)ls_->cols.size();
+        const int nb = (int)ls_->rows.cols.size();
         std::set<int32_t> used;
         e.collect_channels(&used);
         for (int32_t c : used) PA_REQUIRE(c >= 0 && c < nb + n_probe_channels_, PA_ERR_INVALID_ARGUMENT, "join filter references a channel outside the build and probe pages");
         filter_types_.clear();
-        for (int c = 0; c < nb; c++) filter_types_.push_back(ls_->cols[c].type);
+        for (int c = 0; c < nb; c++) filter_types_.push_back(ls_->rows.cols[c].type);
         for (int c = 0; c < n_probe_channels_; c++) filter_types_.push_back(probe_types_[c]);
         filter_types_.push_back(PA_INTEGER);  // the candidate's index
         filter_used_.assign(filter_types_.size(), false);
@@ -899,7 +842,7 @@ public:
     // candidates (probe_idx, build_pos)[0 .. total) of the probe rows [lo, lo + rows) -> filtered_probe_ / filtered_build_; returns their count
     int32_t apply_filter(int32_t lo, int32_t rows, int32_t total, const int32_t* cand_probe, const int32_t* cand_build, hipStream_t s)
     {
-        const int nb = (int)ls_->cols.size();
+        const int nb = (int)ls_->rows.cols.size();
         std::vector<pa_column> cols(filter_types_.size());
         for (size_t c = 0; c < cols.size(); c++) {
             memset(&cols[c], 0, sizeof(pa_column));
@@ -907,7 +850,7 @@ public:
             cols[c].encoding = filter_types_[c] == PA_VARCHAR ? PA_VARWIDTH : PA_FLAT;
             if (!filter_used_[c] && (int)c != nb + n_probe_channels_) continue;
             OutColumn& oc = pair_cols_[c];
-            if ((int)c < nb) gather_column(ls_->cols[c].view(), cand_build, total, oc, s);
+            if ((int)c < nb) gather_column(ls_->rows.view(c), cand_build, total, oc, s);
             else if ((int)c < nb + n_probe_channels_) gather_column(rows_from(in_.cols[c - nb], lo), cand_probe, total, oc, s);
             else {
                 oc.type = PA_INTEGER;
@@ -1014,7 +957,7 @@ private:
     int hash_channel_ = -1, output_mem_ = PA_MEM_HOST;
     DevPage in_;
     bool in_volatile_ = false;
-    std::vector<DevBuf> kept_;  // keep_input: per channel values, offsets, NULL flags
+    HeldRows kept_;   // keep_input: the probe page's channels, when the page outlives the call that brought it
     DevBuf ctl_buf_, hash_, head_, counts_, probe_idx_, build_pos_, scan_temp_, totals_;
     PositionGather gather_;   // (the VARCHAR output channels' copyPositions)
     PinnedBuf h_totals_;
@@ -1078,7 +1021,7 @@ public:
         if (done_ || !ls_->built.load()) return false;
         done_ = true;
         hipStream_t s = stream_.get();
-        const int64_t n = ls_->n;
+        const int64_t n = ls_->n();
         if (n == 0) return false;
         int32_t* part = static_cast<int32_t*>(part_.ensure((size_t)n * 4));
         int32_t* pos = static_cast<int32_t*>(pos_.ensure((size_t)n * 4));
@@ -1107,8 +1050,8 @@ public:
                 PA_HIP(hipMemsetAsync(o.values.ensure((size_t)count * type_width(t)), 0, (size_t)count * type_width(t), s));
             }
         }
-        // (no 2 GiB message: the unvisited build rows, each once, out of a build column of at most INT32_MAX bytes -- HashBuilder::add_input)
-        for (int c : ls_->output_channels) gather_.copy_positions(ls_->cols[c].view(), pos, count, out_cols_[oc++], s);
+        // (no 2 GiB message: the unvisited build rows, each once, out of a build column of at most INT32_MAX bytes -- HeldRows::append_offsets)
+        for (int c : ls_->output_channels) gather_.copy_positions(ls_->rows.view(c), pos, count, out_cols_[oc++], s);
         publish_output(out_cols_, count, output_mem_, s, out, out_storage_);
         return true;
     }
@@ -1155,7 +1098,7 @@ void lookup_source_fill_bitmap(pa_lookup_source* ls, int64_t min_key, uint64_t r
     PA_REQUIRE(ls != nullptr && ls->impl && bits != nullptr, PA_ERR_INVALID_ARGUMENT, "null argument");
     PA_REQUIRE(ls->impl->built.load() && ls->impl->keyed, PA_ERR_ILLEGAL_STATE, "needs a built lookup source with one integer join key");
     const JoinKeys bk = ls->impl->build_keys();
-    launch_join_key_bitmap(bk.col[0], ls->impl->n, min_key, range, bits, s);
+    launch_join_key_bitmap(bk.col[0], ls->impl->n(), min_key, range, bits, s);
 }
 
 // The dynamic filter of a partitioned join: every rank holds the build keys of its own partition, and the probe side is
@@ -1171,7 +1114,7 @@ bool lookup_source_shared_bitmap(pa_lookup_source* ls, pa_comm* comm, bool parti
     // [min key, -max key, "this rank cannot take part"] -> MIN / MIN / MAX; rows -> SUM
     int64_t ends[2] = {has ? impl.key_min : big, has ? -impl.key_max : big};
     int64_t flags[1] = {impl.keyed ? 0 : 1};
-    int64_t rows[1] = {impl.n};
+    int64_t rows[1] = {impl.n()};
     comm_all_reduce_i64(comm, ends, 2, COMM_MIN, s);
     comm_all_reduce_i64(comm, flags, 1, COMM_MAX, s);
     comm_all_reduce_i64(comm, rows, 1, COMM_SUM, s);
@@ -1184,7 +1127,7 @@ bool lookup_source_shared_bitmap(pa_lookup_source* ls, pa_comm* comm, bool parti
     uint64_t* b = static_cast<uint64_t*>(impl.shared_bits.ensure((size_t)words * 8));
     if (has) {
         const JoinKeys bk = impl.build_keys();
-        launch_join_key_bitmap(bk.col[0], impl.n, lo, r, b, s);
+        launch_join_key_bitmap(bk.col[0], impl.n(), lo, r, b, s);
     }
     else PA_HIP(hipMemsetAsync(b, 0, (size_t)words * 8, s));
     if (comm->world > 1) {
@@ -1236,7 +1179,7 @@ int32_t lookup_join_last_pairs(pa_operator* op, const int32_t** probe_idx, const
 int32_t lookup_source_position_count(pa_lookup_source* ls)
 {
     PA_REQUIRE(ls != nullptr && ls->impl != nullptr && ls->impl->built.load(), PA_ERR_ILLEGAL_STATE, "lookup source is not built");
-    return ls->impl->n;
+    return ls->impl->n();
 }
 
 // key[] / positionLinks[] of a built lookup source (tests: chain order parity with the reference)
@@ -1247,7 +1190,7 @@ int32_t lookup_source_tables(pa_lookup_source* ls, const int32_t** key, int32_t*
     if (!impl.reference_built) {
         // keyed joins probe their own table; PagesHash.key[] is made here, for whoever wants to compare it with the reference.
         // The chains are the ones in use: both constructions leave a key's highest position as head and link downwards.
-        const int32_t n = impl.n;
+        const int32_t n = impl.n();
         const JoinKeys bk = impl.build_keys();
         DevBuf slot_scratch, link_scratch, err;
         fill_raw_hash(impl, bk, n, nullptr);
@@ -1263,7 +1206,7 @@ int32_t lookup_source_tables(pa_lookup_source* ls, const int32_t** key, int32_t*
     *key = ls->impl->key.as<int32_t>();
     *hash_size = (int32_t)(ls->impl->mask + 1);
     *links = ls->impl->links.as<int32_t>();
-    *positions = ls->impl->n;
+    *positions = ls->impl->n();
     return PA_OK;
 }
 

@@ -430,9 +430,7 @@ public:
         const int64_t bound = max_output_rows();
         const bool several = m > bound || (int64_t)in_.n > std::max<int64_t>(1, bound / m);
         if (several && page->mem == PA_MEM_DEVICE && (page->flags & PA_PAGE_STABLE) == 0) {
-            kept_.rows = 0;
-            std::fill(kept_.var_bytes.begin(), kept_.var_bytes.end(), 0);
-            for (OutColumn& o : kept_.cols) o.has_nulls = false;
+            kept_.reset();
             kept_.append_page(in_, in_.n, s);
             for (size_t c = 0; c < needed_.size(); c++) {
                 if (needed_[c]) in_.cols[c] = kept_.view((int32_t)c);

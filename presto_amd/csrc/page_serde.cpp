@@ -197,6 +197,7 @@ int64_t serialize_page(const pa_page* page, void* out_host, int64_t capacity, hi
             if (n > 0) {
                 launch_varwidth_ends(col.offsets, n, static_cast<int32_t*>(ends.ensure((size_t)n * 4)), s);
                 PA_HIP(hipMemcpyAsync(w.reserve(n * 4), ends.ptr(), (size_t)n * 4, hipMemcpyDeviceToHost, s));
+                // (the block's two ends, as read_offset_ends reads them -- spelled out here to share the synchronisation of the copy above)
                 PA_HIP(hipMemcpyAsync(&h[0], col.offsets, 4, hipMemcpyDeviceToHost, s));
                 PA_HIP(hipMemcpyAsync(&h[1], col.offsets + n, 4, hipMemcpyDeviceToHost, s));
                 PA_HIP(hipStreamSynchronize(s));

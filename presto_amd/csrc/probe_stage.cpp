@@ -16,7 +16,7 @@ int check_probe_join(const pa_lookup_join_desc& jd, const pa_lookup_source* brid
     PA_REQUIRE(kc >= 0 && kc < n_probe, PA_ERR_INVALID_ARGUMENT, "probe join channel out of range");
     const int32_t kt = probe_types[(size_t)kc];
     PA_REQUIRE(kt == PA_BIGINT || kt == PA_INTEGER || kt == PA_DATE, PA_ERR_NOT_SUPPORTED, "the fused probe takes a BIGINT / INTEGER / DATE key");
-    PA_REQUIRE(kt == ls.cols[(size_t)ls.join_channels[0]].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
+    PA_REQUIRE(kt == ls.rows.cols[(size_t)ls.join_channels[0]].type, PA_ERR_INVALID_ARGUMENT, "probe / build join key types differ");
     for (int32_t i = 0; i < jd.probe_output_channel_count; i++) {
         const int c = jd.probe_output_channels[i];
         PA_REQUIRE(c >= 0 && c < n_probe, PA_ERR_INVALID_ARGUMENT, "probe output channel out of range");
@@ -26,7 +26,7 @@ int check_probe_join(const pa_lookup_join_desc& jd, const pa_lookup_source* brid
 
 int ProbeStage::add_build_column(int col)
 {
-    const int32_t t = ls->cols[(size_t)col].type;
+    const int32_t t = ls->rows.cols[(size_t)col].type;
     // (said when the operator is created, not by the code generator at the first page: such a join runs as the operator chain)
     PA_REQUIRE(t != PA_VARCHAR, PA_ERR_NOT_SUPPORTED, "VARCHAR build columns are not read by the fused probe");
     PA_REQUIRE(t != PA_DECIMAL && t != PA_LONG_DECIMAL, PA_ERR_NOT_SUPPORTED, "DECIMAL build columns are not read by the fused probe");
@@ -61,7 +61,7 @@ void ProbeStage::append_build_channels(std::vector<ChannelLayout>* layout, std::
     for (size_t v = 0; v < build_cols.size(); v++) {
         ChannelLayout cl;
         cl.type = build_types[v];
-        cl.nullable = ls->cols[(size_t)build_cols[v]].has_nulls;  // fixed since the build
+        cl.nullable = ls->rows.cols[(size_t)build_cols[v]].has_nulls;  // fixed since the build
         layout->push_back(cl);
         if (sig) *sig += cl.nullable ? 'N' : '_';
     }

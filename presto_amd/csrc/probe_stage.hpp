@@ -19,7 +19,7 @@ namespace pa {
 
 struct ProbeStage {
     std::shared_ptr<LookupSourceImpl> ls;
-    std::vector<int> build_cols;       // virtual channel n_in + v reads ls->cols[build_cols[v]] at the build position
+    std::vector<int> build_cols;       // virtual channel n_in + v reads ls->rows.cols[build_cols[v]] at the build position
     std::vector<int32_t> build_types;
 
     // build column `col` becomes a virtual channel: its v.  (What an operator adds is its own choice: the aggregation the columns it
@@ -55,9 +55,9 @@ void fill_probe_args(A& a, const ProbeStage& ps)
     a.jrank = reinterpret_cast<const pa_u32x4*>(ls.rank.words);
     a.jrank_rows = ls.rank.rows;
     for (size_t v = 0; v < ps.build_cols.size(); v++) {
-        const BuildColumn& bc = ls.cols[(size_t)ps.build_cols[v]];
-        a.bv[v] = bc.values.ptr();
-        a.bn[v] = bc.has_nulls ? bc.nulls.as<uint8_t>() : nullptr;
+        const DevColumn bc = ls.rows.view(ps.build_cols[v]);
+        a.bv[v] = bc.values;
+        a.bn[v] = bc.nulls;
     }
 }
 
